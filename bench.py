@@ -15,8 +15,13 @@ Multi-GPU: stripes shard; each rank owns its batch end-to-end (weak
 scaling); torch.distributed (RCCL) is used only for barriers and the
 max-over-ranks timing reduction — no data-path collective.
 
-Every measured run is preceded by a bit-exact parity check of sampled
-stripes against the CPU oracle (BASELINE.md "Parity").
+A plain run sets up, warms up, times the steps and prints the result
+line. --full adds everything else the flagship run reports: the bit-exact
+parity check of sampled stripes against the CPU oracle before measuring
+(BASELINE.md "Parity") and the host `cpu_baseline` leg. --dump-outputs DIR
+writes a fixed, seeded sample of what the last timed step left in the
+batch (parity chunks from the encode leg, rebuilt chunks from the decode
+leg) as float32 .npy files, for output-for-output comparison of two builds.
 """
 import argparse
 import json
@@ -80,6 +85,47 @@ def parity_selfcheck(ctx, dptr, args, seed, sample_stripes=2):
             if not np.array_equal(got, want[j]):
                 raise AssertionError(
                     f"stripe {s}: GPU parity {j} mismatches oracle")
+
+
+DUMP_BUDGET_BYTES = 48 * 1000 * 1000  # of float32 on disk; cap is 64 MB
+
+
+def dump_outputs(ctx, dptr, args, erased, out_dir, suffix=""):
+    """Write what the last timed step left in the batch, as the caller of
+    encode_batch/decode_batch receives it (in place): the m parity chunks
+    (encode leg) and the erased chunks (decode leg) of a fixed, seeded
+    sample of stripes. The batch is tens of GiB, so per sampled chunk three
+    windows are kept (head, tail, one seeded interior offset) - tile edges
+    and both ends of the batch are always in the sample. Decode rebuilds
+    in place over chunks the step never wiped, so a right decode leaves
+    them as they were. Values are the bytes 0..255 as float32; the sample
+    depends only on the arguments."""
+    import ctypes
+    k, m, C, S = args.k, args.m, args.chunk_bytes, args.stripes
+    n = k + m
+    rng = np.random.default_rng(args.seed)
+    stripes = sorted({0, S - 1} | set(
+        rng.choice(S, size=min(S, 14), replace=False).tolist()))
+    n_chunks = m + len(erased)
+    per_window = DUMP_BUDGET_BYTES // 4 // (len(stripes) * n_chunks * 3)
+    W = min(C, max(16, per_window // 16 * 16))
+    mid = [int(rng.integers(0, (C - W) // 16 + 1)) * 16 for _ in stripes]
+
+    def sample(chunk_ids):
+        out = np.empty((len(stripes), len(chunk_ids), 3, W), dtype=np.float32)
+        host = np.empty(W, dtype=np.uint8)
+        for si, s in enumerate(stripes):
+            for ci, c in enumerate(chunk_ids):
+                base = dptr.value + (s * n + c) * C
+                for wi, off in enumerate((0, mid[si], C - W)):
+                    ctx.download(host, ctypes.c_void_p(base + off))
+                    out[si, ci, wi] = host
+        return out
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"parity{suffix}.npy"),
+            sample(list(range(k, n))))
+    np.save(os.path.join(out_dir, f"decoded{suffix}.npy"), sample(erased))
 
 
 def _set_omp_threads(n):
@@ -380,7 +426,7 @@ def bench_lrc(args):
         ctx.sync()
 
     step()  # warm + correctness pass below
-    if not args.no_selfcheck:
+    if args.full and not args.no_selfcheck:
         import oracle
         host = np.zeros(n * C, dtype=np.uint8)
         ctx.download(host, d)  # stripe 0
@@ -524,8 +570,18 @@ def main():
                     help="emit the per-rank run plan and exit (no GPU)")
     ap.add_argument("--erasures", type=int, default=3)
     ap.add_argument("--seed", type=lambda x: int(x, 0), default=0xEC)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-selfcheck", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the pre-measurement parity self-check "
+                         "against the CPU oracle and the host cpu_baseline "
+                         "leg (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a seeded sample of "
+                         "the last step's outputs as DIR/<name>.npy "
+                         "(float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-selfcheck", action="store_true",
+                    help="with --full: skip the parity self-check")
     ap.add_argument("--streams", type=int, default=2)
     ap.add_argument("--threads", type=int, default=1,
                     help="concurrent host-path callers (hostpath preset)")
@@ -537,6 +593,11 @@ def main():
                          "sweep w/ latency histogram, hostpath=PCIe "
                          "plugin-path probe")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.config not in ("rs83", "cauchy104"):
+        ap.error("--dump-outputs covers the device-resident batch presets "
+                 "(rs83, cauchy104) only")
     args.chunk_bytes = args.chunk_kib * 1024
     if args.config == "cauchy104":
         args.k, args.m, args.technique, args.erasures = 10, 4, "cauchy", 4
@@ -627,9 +688,10 @@ def main():
             dec_accum.append(ctx.last_kernel_ms())
         ctx.sync()
 
-    # parity self-check before measuring (rank 0)
+    # one untimed pass (first-launch costs stay out of --warmup 0 runs);
+    # --full: parity self-check of its result before measuring (rank 0)
     step()
-    if rank == 0 and not args.no_selfcheck:
+    if args.full and rank == 0 and not args.no_selfcheck:
         parity_selfcheck(ctx, dptr, args, seed)
 
     for _ in range(args.warmup):
@@ -652,6 +714,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
         dist.barrier()
+
+    if args.dump_outputs:
+        dump_outputs(ctx, dptr, args, erased, args.dump_outputs,
+                     suffix=f"_rank{rank}" if world > 1 else "")
 
     if rank == 0:
         input_bytes_per_step = 2 * k * C * S  # encode + decode accounting
@@ -703,7 +769,8 @@ def main():
                 "decode_alg_bytes": (k + len(erased)) * C * S,
             },
             "cpu_baseline": (cpu_baseline(args)
-                             if (world == 1 and not args.no_cpu_baseline
+                             if (args.full and world == 1
+                                 and not args.no_cpu_baseline
                                  and args.technique in
                                  ("reed_sol_van", "cauchy",
                                   "jerasure_reed_sol_van"))

@@ -47,3 +47,19 @@ def test_driver_flag_shapes():
     d = dry({"RANK": "3", "WORLD_SIZE": "4", "LOCAL_RANK": "3"},
             "--gpus", "4", "--steps", "10", "--warmup", "3")
     assert d["steps"] == 10 and d["warmup"] == 3 and d["rank"] == 3
+
+
+def test_full_and_dump_flags_parse(tmp_path):
+    """--full and --dump-outputs DIR are accepted next to the driver's
+    flags; a dry run writes nothing."""
+    out = tmp_path / "dump"
+    d = dry(None, "--gpus", "1", "--steps", "4", "--warmup", "2", "--full",
+            "--dump-outputs", str(out))
+    assert d["steps"] == 4 and d["warmup"] == 2
+    assert not out.exists()
+
+
+def test_zero_steps_rejected():
+    r = subprocess.run([sys.executable, BENCH, "--dry-run", "--steps", "0"],
+                       capture_output=True, text=True, cwd=ROOT)
+    assert r.returncode == 2 and "--steps" in r.stderr
