@@ -87,6 +87,20 @@ def _lib():
                                       ctypes.POINTER(ctypes.c_size_t),
                                       ctypes.c_int, ctypes.c_uint64,
                                       ctypes.c_int]
+    lib.ecx_decode_batch_multi.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_long, ctypes.c_size_t,
+                                           ctypes.POINTER(ctypes.c_uint64),
+                                           ctypes.c_int]
+    lib.ecx_decode_slices_multi.argtypes = [ctypes.c_void_p,
+                                            ctypes.POINTER(ctypes.c_void_p),
+                                            ctypes.POINTER(ctypes.c_size_t),
+                                            ctypes.c_int,
+                                            ctypes.POINTER(ctypes.c_uint64),
+                                            ctypes.c_int]
+    lib.ecx_decode_multi_plan_probe.argtypes = [
+        ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        ctypes.POINTER(ctypes.c_uint64), ctypes.c_long,
+        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.ecx_set_matrix.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.ecx_matmul_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_long, ctypes.c_size_t,
@@ -145,6 +159,41 @@ def _ck(r, what):
     if isinstance(r, int) and r < 0:
         raise EcError(f"{what}: {_ERR.get(r, r)}")
     return r
+
+
+def _mask_array(masks, n, what):
+    """Per-stripe present masks (any integer sequence or a np.uint64
+    array) as a contiguous uint64 array of exactly n entries."""
+    a = np.asarray(masks)
+    if a.size and (a.dtype.kind not in "iu" or
+                   (a.dtype.kind == "i" and a.min() < 0)):
+        raise EcError(f"{what}: present_masks must be integers that fit "
+                      f"uint64 (got dtype {a.dtype})")
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    if a.ndim != 1 or a.shape[0] != n:
+        raise EcError(f"{what}: need {n} present_masks (one per stripe or "
+                      f"slice), got shape {a.shape}")
+    return a
+
+
+def _u64p(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+
+
+def decode_multi_plan_probe(technique, k, m, masks):
+    """CPU-only: how decode_batch_multi / decode_slices_multi would group
+    these per-stripe masks. Returns (n_launches, plan_of_stripe, n_plans);
+    plan_of_stripe[s] is the index of stripe s's mask among the distinct
+    masks in first-appearance order, -1 if nothing is erased."""
+    t = TECHNIQUES[technique] if isinstance(technique, str) else technique
+    a = _mask_array(masks, len(masks), "ecx_decode_multi_plan_probe")
+    pos = np.zeros(max(len(a), 1), dtype=np.int32)
+    n_plans = ctypes.c_int()
+    r = _ck(lib().ecx_decode_multi_plan_probe(
+        t, k, m, _u64p(a), len(a),
+        pos.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+        ctypes.byref(n_plans)), "ecx_decode_multi_plan_probe")
+    return r, pos[:len(a)], n_plans.value
 
 
 def _ptr_array(bufs):
@@ -256,6 +305,27 @@ class EcContext:
         arr, sz, n = self._slice_args(chunk_ptrs, sizes)
         _ck(lib().ecx_decode_slices(self._h, arr, sz, n, present_mask,
                                     slot), "ecx_decode_slices")
+
+    def decode_batch_multi(self, dptr, n_stripes, chunk_bytes, present_masks,
+                           slot=0):
+        """decode_batch with one present mask PER STRIPE (recovery batches
+        whose neighbouring stripes miss different chunks). Launch count is
+        independent of the number of distinct masks, at most m."""
+        a = _mask_array(present_masks, n_stripes, "ecx_decode_batch_multi")
+        _ck(lib().ecx_decode_batch_multi(self._h, dptr, n_stripes,
+                                         chunk_bytes, _u64p(a), slot),
+            "ecx_decode_batch_multi")
+
+    def decode_slices_multi(self, chunk_ptrs, sizes, present_masks, slot=0):
+        """decode_slices with one present mask per slice."""
+        if len(chunk_ptrs) != len(sizes) * (self.k + self.m):
+            raise EcError(f"ecx_decode_slices_multi: {len(sizes)} slices "
+                          f"need {len(sizes) * (self.k + self.m)} chunk "
+                          f"pointers, got {len(chunk_ptrs)}")
+        a = _mask_array(present_masks, len(sizes), "ecx_decode_slices_multi")
+        arr, sz, n = self._slice_args(chunk_ptrs, sizes)
+        _ck(lib().ecx_decode_slices_multi(self._h, arr, sz, n, _u64p(a),
+                                          slot), "ecx_decode_slices_multi")
 
     def matmul_batch(self, dptr, n_stripes, chunk_bytes, src_ids, out_ids,
                      rows, slot=0):

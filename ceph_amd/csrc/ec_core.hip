@@ -46,6 +46,7 @@
 
 #include "../../include/ec_mi355x.h"
 #include "gf.h"
+#include "decode_multi.h"
 
 // ---------------------------------------------------------------------------
 // Kernel-side
@@ -272,6 +273,272 @@ __global__ __launch_bounds__(256, 2) void ec_gf_slices_kernel(
   __shared__ int s_out[ECX_MAX_OUT];
   __shared__ uint8_t s_cls[ECX_MAX_OUT * ECX_MAX_K];
   const int n_src = pb->n_src;
+  for (int t = threadIdx.x; t < NOUT * n_src * 6; t += blockDim.x)
+    s_tabs[t] = pb->tabs[t];
+  for (int t = threadIdx.x; t < n_src; t += blockDim.x)
+    s_src[t] = pb->src_ids[t];
+  for (int t = threadIdx.x; t < NOUT; t += blockDim.x)
+    s_out[t] = pb->out_ids[t];
+  for (int t = threadIdx.x; t < NOUT * n_src; t += blockDim.x)
+    s_cls[t] = pb->cls[t];
+  __syncthreads();
+
+  const int sl = block_slice[blockIdx.x];
+  const long v0 = block_voff[blockIdx.x];
+  const long nv = slice_vecs[sl];
+  const long vend = v0 + vecs_per_block < nv ? v0 + vecs_per_block : nv;
+  const uint64_t* ptrs = chunk_ptrs + (long)sl * cps;
+
+  for (long p = v0 + threadIdx.x; p < vend; p += blockDim.x) {
+    const long off = p << 4;
+    uint32_t acc[NOUT][4];
+#pragma unroll
+    for (int j = 0; j < NOUT; j++)
+      acc[j][0] = acc[j][1] = acc[j][2] = acc[j][3] = 0u;
+
+    for (int i = 0; i < n_src; i++) {
+      const uint8_t* sp = (const uint8_t*)ptrs[s_src[i]];
+      if (sp == nullptr) continue;  // zeros chunk for this slice
+      const v4u* p4 = reinterpret_cast<const v4u*>(sp + off);
+      const v4u d = NT ? __builtin_nontemporal_load(p4) : *p4;
+      const uint32_t dq[4] = {d.x, d.y, d.z, d.w};
+      uint32_t i7l[4], i7h[4], i8[4];
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        i7l[q] = dq[q] & 0x07070707u;
+        i7h[q] = (dq[q] >> 4) & 0x07070707u;
+        i8[q] = ((dq[q] >> 3) & 0x01010101u) |
+                ((dq[q] >> 6) & 0x02020202u);
+      }
+#pragma unroll
+      for (int j = 0; j < NOUT; j++) {
+        const int cls = __builtin_amdgcn_readfirstlane(s_cls[j * n_src + i]);
+        if (cls == 0) continue;
+        if (cls == 1) {
+#pragma unroll
+          for (int q = 0; q < 4; q++) acc[j][q] ^= dq[q];
+        } else {
+          const uint32_t* T = &s_tabs[(j * n_src + i) * 6];
+          const uint32_t l0 = T[0], l1 = T[1], h0 = T[2], h1 = T[3],
+                         w8 = T[4];
+#pragma unroll
+          for (int q = 0; q < 4; q++)
+            acc[j][q] ^= ecx_gfmul4(l0, l1, h0, h1, w8, i7l[q], i7h[q],
+                                    i8[q]);
+        }
+      }
+    }
+
+#pragma unroll
+    for (int j = 0; j < NOUT; j++) {
+      v4u o;
+      o.x = acc[j][0]; o.y = acc[j][1]; o.z = acc[j][2]; o.w = acc[j][3];
+      v4u* p4 = reinterpret_cast<v4u*>((uint8_t*)ptrs[s_out[j]] + off);
+      if (NT)
+        __builtin_nontemporal_store(o, p4);
+      else
+        *p4 = o;
+    }
+  }
+}
+
+// ---- per-stripe erasure patterns (ecx_decode_*_multi) ----
+// A recovery batching shim collects degraded reads from many placement
+// groups, so neighbouring stripes of one batch miss different chunks. The
+// kernels above take ONE parameter block per launch; these variants take a
+// device-resident table of compact launch records and let every block pick
+// its own: blockIdx.y -> stripe_list[y] -> plan_of_stripe[stripe] -> record.
+// The host buckets stripes by output count (NOUT is a template parameter),
+// so the number of launches is independent of how many patterns the call
+// holds (decode_multi.h). Record load costs the same as the load from `pb`
+// above; cls stays wave-uniform because the record is per block.
+#define ECX_MULTI_OUT 4  // == ecx::MULTI_MAX_OUT
+
+// One <= 4-output pass of one erasure pattern: fill_params' output cut down
+// to the 4 outputs a launch can carry (3.3 KB instead of 7.3 KB — the table
+// holds one per distinct pattern and pass and is uploaded per call).
+struct EcMultiRec {
+  int src_ids[ECX_MAX_K];
+  int out_ids[ECX_MULTI_OUT];
+  uint8_t cls[ECX_MULTI_OUT * ECX_MAX_K];        // [j * n_src + i]
+  uint32_t tabs[ECX_MULTI_OUT * ECX_MAX_K * 6];  // [(j * n_src + i) * 6]
+};
+
+// Body is ec_gf_matmul_kernel's (ACCUM = false, KN = 0) — kept as a separate
+// kernel so the uniform-pattern instances the flagship numbers rest on are
+// compiled from untouched source. Decode is in place: sources (survivors)
+// and outputs (erased) of a stripe are disjoint chunks, so buf/obuf may
+// both be __restrict__ and passes of one stripe do not interfere.
+template <int NOUT, int VPT, bool NT, int PF>
+__global__ __launch_bounds__(256, 2) void ec_gf_matmul_multi_kernel(
+    const uint8_t* __restrict__ buf, uint8_t* __restrict__ obuf,
+    const EcMultiRec* __restrict__ recs,       // [n_plans * n_pass]
+    const int* __restrict__ plan_of_stripe,    // [n_stripes]
+    const int* __restrict__ stripe_list,       // [gridDim.y]
+    int n_src, int pass, int n_pass, long chunk_bytes, int chunks_per_stripe,
+    long vecs_per_chunk) {
+  __shared__ uint32_t s_tabs[ECX_MULTI_OUT * ECX_MAX_K * 6];
+  __shared__ int s_src[ECX_MAX_K];
+  __shared__ int s_out[ECX_MULTI_OUT];
+  __shared__ uint8_t s_cls[ECX_MULTI_OUT * ECX_MAX_K];
+  const long stripe = stripe_list[blockIdx.y];
+  const EcMultiRec* pb =
+      recs + ((long)plan_of_stripe[stripe] * n_pass + pass);
+  for (int t = threadIdx.x; t < NOUT * n_src * 6; t += blockDim.x)
+    s_tabs[t] = pb->tabs[t];
+  for (int t = threadIdx.x; t < n_src; t += blockDim.x)
+    s_src[t] = pb->src_ids[t];
+  for (int t = threadIdx.x; t < NOUT; t += blockDim.x)
+    s_out[t] = pb->out_ids[t];
+  for (int t = threadIdx.x; t < NOUT * n_src; t += blockDim.x)
+    s_cls[t] = pb->cls[t];
+  __syncthreads();
+
+  const uint8_t* sbase = buf + stripe * chunks_per_stripe * chunk_bytes;
+  uint8_t* obase = obuf + stripe * chunks_per_stripe * chunk_bytes;
+
+  for (long p0 = (long)blockIdx.x * blockDim.x * VPT + threadIdx.x;
+       p0 < vecs_per_chunk; p0 += (long)gridDim.x * blockDim.x * VPT) {
+    long off[VPT];
+    bool live[VPT];
+#pragma unroll
+    for (int v = 0; v < VPT; v++) {
+      long p = p0 + (long)v * blockDim.x;
+      live[v] = p < vecs_per_chunk;
+      off[v] = p << 4;
+    }
+    uint32_t acc[NOUT][VPT][4];
+#pragma unroll
+    for (int j = 0; j < NOUT; j++)
+#pragma unroll
+      for (int v = 0; v < VPT; v++)
+        acc[j][v][0] = acc[j][v][1] = acc[j][v][2] = acc[j][v][3] = 0u;
+
+    uint32_t dnf[PF ? PF : 1][VPT][4];
+#pragma unroll
+    for (int pd = 0; pd < PF; pd++) {
+      const int si = pd < n_src ? pd : n_src - 1;
+      const uint8_t* sp0 = sbase + (long)s_src[si] * chunk_bytes;
+#pragma unroll
+      for (int v = 0; v < VPT; v++) {
+        v4u d = {0, 0, 0, 0};
+        if (live[v]) {
+          const v4u* p4 = reinterpret_cast<const v4u*>(sp0 + off[v]);
+          d = NT ? __builtin_nontemporal_load(p4) : *p4;
+        }
+        dnf[pd][v][0] = d.x; dnf[pd][v][1] = d.y;
+        dnf[pd][v][2] = d.z; dnf[pd][v][3] = d.w;
+      }
+    }
+    for (int i = 0; i < n_src; i++) {
+      const uint8_t* sp = sbase + (long)s_src[i] * chunk_bytes;
+      uint32_t dq[VPT][4];
+      uint32_t i7l[VPT][4], i7h[VPT][4], i8[VPT][4];
+#pragma unroll
+      for (int v = 0; v < VPT; v++) {
+        v4u d = {0, 0, 0, 0};
+        if (PF) {
+          d.x = dnf[0][v][0]; d.y = dnf[0][v][1];
+          d.z = dnf[0][v][2]; d.w = dnf[0][v][3];
+        } else if (live[v]) {
+          const v4u* p4 = reinterpret_cast<const v4u*>(sp + off[v]);
+          d = NT ? __builtin_nontemporal_load(p4) : *p4;
+        }
+        dq[v][0] = d.x; dq[v][1] = d.y; dq[v][2] = d.z; dq[v][3] = d.w;
+      }
+      if (PF) {
+        // rotate the prefetch ring and issue source i+PF
+#pragma unroll
+        for (int pd = 0; pd + 1 < PF; pd++)
+#pragma unroll
+          for (int v = 0; v < VPT; v++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) dnf[pd][v][q] = dnf[pd + 1][v][q];
+        if (i + PF < n_src) {
+          const uint8_t* spn = sbase + (long)s_src[i + PF] * chunk_bytes;
+#pragma unroll
+          for (int v = 0; v < VPT; v++) {
+            v4u d = {0, 0, 0, 0};
+            if (live[v]) {
+              const v4u* p4 = reinterpret_cast<const v4u*>(spn + off[v]);
+              d = NT ? __builtin_nontemporal_load(p4) : *p4;
+            }
+            dnf[PF ? PF - 1 : 0][v][0] = d.x;
+            dnf[PF ? PF - 1 : 0][v][1] = d.y;
+            dnf[PF ? PF - 1 : 0][v][2] = d.z;
+            dnf[PF ? PF - 1 : 0][v][3] = d.w;
+          }
+        }
+      }
+#pragma unroll
+      for (int v = 0; v < VPT; v++) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          i7l[v][q] = dq[v][q] & 0x07070707u;
+          i7h[v][q] = (dq[v][q] >> 4) & 0x07070707u;
+          i8[v][q] = ((dq[v][q] >> 3) & 0x01010101u) |
+                     ((dq[v][q] >> 6) & 0x02020202u);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < NOUT; j++) {
+        // uniform across the wave (one record per block): scalar branch
+        const int cls = __builtin_amdgcn_readfirstlane(s_cls[j * n_src + i]);
+        if (cls == 0) continue;
+        if (cls == 1) {
+#pragma unroll
+          for (int v = 0; v < VPT; v++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) acc[j][v][q] ^= dq[v][q];
+        } else {
+          const uint32_t* T = &s_tabs[(j * n_src + i) * 6];
+          const uint32_t l0 = T[0], l1 = T[1], h0 = T[2], h1 = T[3],
+                         w8 = T[4];
+#pragma unroll
+          for (int v = 0; v < VPT; v++)
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+              acc[j][v][q] ^= ecx_gfmul4(l0, l1, h0, h1, w8, i7l[v][q],
+                                         i7h[v][q], i8[v][q]);
+        }
+      }
+    }
+
+#pragma unroll
+    for (int j = 0; j < NOUT; j++)
+#pragma unroll
+      for (int v = 0; v < VPT; v++) {
+        if (!live[v]) continue;
+        v4u o;
+        o.x = acc[j][v][0]; o.y = acc[j][v][1];
+        o.z = acc[j][v][2]; o.w = acc[j][v][3];
+        v4u* p4 = reinterpret_cast<v4u*>(obase + (long)s_out[j] * chunk_bytes +
+                                         off[v]);
+        if (NT)
+          __builtin_nontemporal_store(o, p4);
+        else
+          *p4 = o;
+      }
+  }
+}
+
+// Slices form: the per-block (slice, voff) table gains the record index;
+// the host buckets the block lists by output count like the stripe lists
+// above. A NULL survivor pointer still means zeros for that slice only.
+template <int NOUT, bool NT>
+__global__ __launch_bounds__(256, 2) void ec_gf_slices_multi_kernel(
+    const uint64_t* __restrict__ chunk_ptrs,  // [n_slices * cps]
+    const int* __restrict__ block_slice,      // [gridDim.x]
+    const long* __restrict__ block_voff,      // [gridDim.x]
+    const int* __restrict__ block_rec,        // [gridDim.x]
+    const long* __restrict__ slice_vecs,      // [n_slices]
+    const EcMultiRec* __restrict__ recs, int n_src, int cps,
+    int vecs_per_block) {
+  __shared__ uint32_t s_tabs[ECX_MULTI_OUT * ECX_MAX_K * 6];
+  __shared__ int s_src[ECX_MAX_K];
+  __shared__ int s_out[ECX_MULTI_OUT];
+  __shared__ uint8_t s_cls[ECX_MULTI_OUT * ECX_MAX_K];
+  const EcMultiRec* pb = recs + block_rec[blockIdx.x];
   for (int t = threadIdx.x; t < NOUT * n_src * 6; t += blockDim.x)
     s_tabs[t] = pb->tabs[t];
   for (int t = threadIdx.x; t < n_src; t += blockDim.x)
@@ -1968,6 +2235,97 @@ static int get_decode_plan(ecx_ctx* ctx, uint64_t present_mask,
   return ECX_OK;
 }
 
+// ---- per-stripe erasure patterns: host side ----
+static_assert(ECX_MULTI_OUT == ecx::MULTI_MAX_OUT, "kernel/grouping split");
+static_assert(sizeof(EcMultiRec) % 8 == 0, "8-byte arrays follow the table");
+
+// Group a call's masks (decode_multi.h) and fetch every distinct mask's
+// plan through the LRU; plans[i] belongs to g.masks[i]. ECX_ERR_IO if any
+// mask is undecodable — before anything is staged or launched.
+static int multi_resolve(ecx_ctx* ctx, const uint64_t* masks, long n,
+                         ecx::MultiGrouping& g,
+                         std::vector<DecodePlan>& plans) {
+  plans.clear();
+  auto resolve = [&](uint64_t mask) {
+    DecodePlan p;
+    if (get_decode_plan(ctx, mask, p) != ECX_OK) return false;
+    plans.push_back(std::move(p));
+    return true;
+  };
+  if (!ecx::group_decode_masks(ctx->k, ctx->m, masks, n, resolve, g))
+    return ECX_ERR_IO;
+  return ECX_OK;
+}
+
+// Launch records [plan * n_pass + pass] from fill_params' output; passes a
+// plan does not have stay zeroed and are never referenced.
+static void multi_fill_recs(EcMultiRec* recs, const ecx::MultiGrouping& g,
+                            const std::vector<DecodePlan>& plans, int k) {
+  const ecx::GF8& f = ecx::gf8();
+  std::memset(recs, 0, sizeof(EcMultiRec) * plans.size() * g.n_pass);
+  for (size_t pl = 0; pl < plans.size(); pl++) {
+    const DecodePlan& dp = plans[pl];
+    const int e = (int)dp.erased.size();
+    for (int pass = 0; pass * ECX_MULTI_OUT < e; pass++) {
+      const int j0 = pass * ECX_MULTI_OUT;
+      const int nj = std::min(ECX_MULTI_OUT, e - j0);
+      EcLaunchParams p;
+      std::memset(&p, 0, sizeof(p));
+      fill_params(&p, f, dp.survivors.data(), k, dp.erased.data() + j0, nj,
+                  dp.rows.data() + (size_t)j0 * k, nullptr);
+      EcMultiRec& r = recs[pl * g.n_pass + pass];
+      std::memcpy(r.src_ids, p.src_ids, sizeof(int) * k);
+      std::memcpy(r.out_ids, p.out_ids, sizeof(int) * nj);
+      std::memcpy(r.cls, p.cls, (size_t)nj * k);
+      std::memcpy(r.tabs, p.tabs, sizeof(uint32_t) * 6 * nj * k);
+    }
+  }
+}
+
+// same policy as matmul_dispatch: one-ahead source prefetch at NOUT >= 4
+static int multi_pf(int n_out) {
+  static const int env_pf = [] {
+    const char* v = getenv("ECX_PF");
+    return v ? atoi(v) : 2;
+  }();
+  return (env_pf == 1 || env_pf == 3) ? 1 : (env_pf == 2 && n_out >= 4) ? 1 : 0;
+}
+
+struct MultiArgs {
+  uint8_t* buf;
+  const EcMultiRec* recs;
+  const int* plan_of_stripe;
+  const int* stripe_list;
+  int n_src, pass, n_pass;
+  long chunk_bytes;
+  int cps;
+  long vecs;
+};
+
+template <int NO, int VP, bool NTF, int PFD>
+static void multi_launch1(dim3 grid, hipStream_t st, const MultiArgs& a) {
+  hipLaunchKernelGGL((ec_gf_matmul_multi_kernel<NO, VP, NTF, PFD>), grid,
+                     dim3(256), 0, st, a.buf, a.buf, a.recs, a.plan_of_stripe,
+                     a.stripe_list, a.n_src, a.pass, a.n_pass, a.chunk_bytes,
+                     a.cps, a.vecs);
+}
+
+template <int NO>
+static void multi_launch(const MatmulCfg& c, int pf, hipStream_t st,
+                         const MultiArgs& a) {
+  if (c.vpt == 2) {
+    if (c.nt) pf ? multi_launch1<NO, 2, true, 1>(c.grid, st, a)
+                 : multi_launch1<NO, 2, true, 0>(c.grid, st, a);
+    else pf ? multi_launch1<NO, 2, false, 1>(c.grid, st, a)
+            : multi_launch1<NO, 2, false, 0>(c.grid, st, a);
+  } else {
+    if (c.nt) pf ? multi_launch1<NO, 1, true, 1>(c.grid, st, a)
+                 : multi_launch1<NO, 1, true, 0>(c.grid, st, a);
+    else pf ? multi_launch1<NO, 1, false, 1>(c.grid, st, a)
+            : multi_launch1<NO, 1, false, 0>(c.grid, st, a);
+  }
+}
+
 extern "C" {
 
 int ecx_encode_batch(ecx_ctx* ctx, void* dptr, long n_stripes,
@@ -2111,6 +2469,226 @@ int ecx_decode_slices(ecx_ctx* ctx, void* const* d_chunks,
   return run_slices(ctx, slot, d_chunks, bytes, n_slices,
                     plan.survivors.data(), ctx->k, plan.erased.data(),
                     (int)plan.erased.size(), plan.rows.data());
+}
+
+int ecx_decode_batch_multi(ecx_ctx* ctx, void* dptr, long n_stripes,
+                           size_t chunk_bytes, const uint64_t* present_masks,
+                           int slot) {
+  if (!ctx || !dptr || !present_masks || slot < 0 ||
+      slot >= (int)ctx->slots.size() || ctx->is_bitmatrix() ||
+      ctx->is_w16() || chunk_bytes == 0 || chunk_bytes % 16 ||
+      n_stripes <= 0 || n_stripes > 65535)
+    return ECX_ERR_INVAL;
+  Slot& s = ctx->slots[slot];
+  std::lock_guard<std::recursive_mutex> g(s.mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+
+  // every mask is resolved (and refused) before anything is staged
+  ecx::MultiGrouping grp;
+  std::vector<DecodePlan> plans;
+  int r = multi_resolve(ctx, present_masks, n_stripes, grp, plans);
+  if (r != ECX_OK) return r;
+  if (grp.launches.empty()) return ECX_OK;  // nothing erased anywhere
+
+  // blob: [records][plan_of_stripe i32][stripe lists i32, launch order]
+  const size_t n_recs = plans.size() * (size_t)grp.n_pass;
+  size_t n_listed = 0;
+  for (const auto& l : grp.launches) n_listed += l.members.size();
+  const size_t off_pos = n_recs * sizeof(EcMultiRec);
+  const size_t off_list = off_pos + (size_t)n_stripes * 4;
+  const size_t blob = off_list + n_listed * 4;
+  r = ensure_jobs(ctx, s, blob);
+  if (r != ECX_OK) return r;
+  HIP_TRY(wait_event(s.ev_jobs));
+  multi_fill_recs((EcMultiRec*)s.h_jobs, grp, plans, ctx->k);
+  std::memcpy(s.h_jobs + off_pos, grp.plan_of_stripe.data(),
+              (size_t)n_stripes * 4);
+  {
+    int* list = (int*)(s.h_jobs + off_list);
+    for (const auto& l : grp.launches) {
+      std::memcpy(list, l.members.data(), l.members.size() * 4);
+      list += l.members.size();
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(s.d_jobs, s.h_jobs, blob, hipMemcpyHostToDevice,
+                         s.stream));
+  HIP_TRY(hipEventRecord(s.ev_jobs, s.stream));
+
+  MultiArgs a;
+  a.buf = (uint8_t*)dptr;
+  a.recs = (const EcMultiRec*)s.d_jobs;
+  a.plan_of_stripe = (const int*)(s.d_jobs + off_pos);
+  a.stripe_list = (const int*)(s.d_jobs + off_list);
+  a.n_src = ctx->k;
+  a.n_pass = grp.n_pass;
+  a.chunk_bytes = (long)chunk_bytes;
+  a.cps = ctx->k + ctx->m;
+  a.vecs = (long)(chunk_bytes >> 4);
+  // one event pair around the whole call, launches back to back
+  HIP_TRY(hipEventRecord(s.ev_start, s.stream));
+  for (const auto& l : grp.launches) {
+    const MatmulCfg c = matmul_cfg(a.vecs, (long)l.members.size());
+    const int pf = multi_pf(l.n_out);
+    a.pass = l.pass;
+    switch (l.n_out) {
+      case 1: multi_launch<1>(c, pf, s.stream, a); break;
+      case 2: multi_launch<2>(c, pf, s.stream, a); break;
+      case 3: multi_launch<3>(c, pf, s.stream, a); break;
+      default: multi_launch<4>(c, pf, s.stream, a); break;
+    }
+    HIP_TRY(hipGetLastError());
+    a.stripe_list += l.members.size();
+  }
+  HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
+  s.timed = true;
+  return ECX_OK;
+}
+
+int ecx_decode_slices_multi(ecx_ctx* ctx, void* const* d_chunks,
+                            const size_t* bytes, int n_slices,
+                            const uint64_t* present_masks, int slot) {
+  if (!ctx || !d_chunks || !bytes || !present_masks || slot < 0 ||
+      slot >= (int)ctx->slots.size() || ctx->is_bitmatrix() ||
+      ctx->is_w16() || n_slices < 1)
+    return ECX_ERR_INVAL;
+  for (int i = 0; i < n_slices; i++)
+    if (bytes[i] == 0 || bytes[i] % 16) return ECX_ERR_INVAL;
+  const int k = ctx->k, cps = ctx->k + ctx->m;
+  Slot& s = ctx->slots[slot];
+  std::lock_guard<std::recursive_mutex> g(s.mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+
+  ecx::MultiGrouping grp;
+  std::vector<DecodePlan> plans;
+  int r = multi_resolve(ctx, present_masks, n_slices, grp, plans);
+  if (r != ECX_OK) return r;
+  // an erased chunk is written: it needs a buffer (NULL only ever means a
+  // zeros SOURCE)
+  for (int i = 0; i < n_slices; i++) {
+    const int pl = grp.plan_of_stripe[i];
+    if (pl < 0) continue;
+    for (int e : plans[pl].erased)
+      if (!d_chunks[(size_t)i * cps + e]) return ECX_ERR_INVAL;
+  }
+  if (grp.launches.empty()) return ECX_OK;
+
+  static const int env_nt = [] {
+    const char* v = getenv("ECX_NT");
+    return v ? atoi(v) : 1;
+  }();
+  const int VECS_PER_BLOCK = 256 * 4;
+  auto blocks_of = [&](int sl) {
+    return (long)((bytes[sl] >> 4) + VECS_PER_BLOCK - 1) / VECS_PER_BLOCK;
+  };
+  long n_blocks = 0;
+  for (const auto& l : grp.launches)
+    for (int sl : l.members) n_blocks += blocks_of(sl);
+  if (n_blocks > (1 << 30)) return ECX_ERR_INVAL;
+
+  // blob: [records][ptrs u64][slice_vecs i64][block_voff i64]
+  // [block_slice i32][block_rec i32]; block tables in launch order
+  const size_t n_recs = plans.size() * (size_t)grp.n_pass;
+  const size_t off_ptrs = n_recs * sizeof(EcMultiRec);
+  const size_t off_vecs = off_ptrs + (size_t)n_slices * cps * 8;
+  const size_t off_voff = off_vecs + (size_t)n_slices * 8;
+  const size_t off_bsl = off_voff + (size_t)n_blocks * 8;
+  const size_t off_brec = off_bsl + (size_t)n_blocks * 4;
+  const size_t blob = off_brec + (size_t)n_blocks * 4;
+  r = ensure_jobs(ctx, s, blob);
+  if (r != ECX_OK) return r;
+  HIP_TRY(wait_event(s.ev_jobs));
+
+  multi_fill_recs((EcMultiRec*)s.h_jobs, grp, plans, k);
+  uint64_t* ptrs = (uint64_t*)(s.h_jobs + off_ptrs);
+  long* svecs = (long*)(s.h_jobs + off_vecs);
+  long* bvoff = (long*)(s.h_jobs + off_voff);
+  int* bslice = (int*)(s.h_jobs + off_bsl);
+  int* brec = (int*)(s.h_jobs + off_brec);
+  for (int i = 0; i < n_slices; i++) {
+    for (int c = 0; c < cps; c++)
+      ptrs[(size_t)i * cps + c] = (uint64_t)d_chunks[(size_t)i * cps + c];
+    svecs[i] = (long)(bytes[i] >> 4);
+  }
+  long b = 0;
+  for (const auto& l : grp.launches)
+    for (int sl : l.members) {
+      const int rec = grp.plan_of_stripe[sl] * grp.n_pass + l.pass;
+      for (long v = 0; v < svecs[sl]; v += VECS_PER_BLOCK) {
+        bslice[b] = sl;
+        bvoff[b] = v;
+        brec[b] = rec;
+        b++;
+      }
+    }
+  HIP_TRY(hipMemcpyAsync(s.d_jobs, s.h_jobs, blob, hipMemcpyHostToDevice,
+                         s.stream));
+  HIP_TRY(hipEventRecord(s.ev_jobs, s.stream));
+
+  const EcMultiRec* d_recs = (const EcMultiRec*)s.d_jobs;
+  const uint64_t* d_ptrs = (const uint64_t*)(s.d_jobs + off_ptrs);
+  const long* d_svecs = (const long*)(s.d_jobs + off_vecs);
+  const long* d_bvoff = (const long*)(s.d_jobs + off_voff);
+  const int* d_bslice = (const int*)(s.d_jobs + off_bsl);
+  const int* d_brec = (const int*)(s.d_jobs + off_brec);
+
+  HIP_TRY(hipEventRecord(s.ev_start, s.stream));
+  long b0 = 0;
+  for (const auto& l : grp.launches) {
+    long nb = 0;
+    for (int sl : l.members) nb += blocks_of(sl);
+#define ECX_SMLAUNCH(NO, NTF)                                               \
+  hipLaunchKernelGGL((ec_gf_slices_multi_kernel<NO, NTF>),                  \
+                     dim3((unsigned)nb), dim3(256), 0, s.stream, d_ptrs,    \
+                     d_bslice + b0, d_bvoff + b0, d_brec + b0, d_svecs,     \
+                     d_recs, k, cps, VECS_PER_BLOCK)
+#define ECX_SMDISPATCH(NO)                  \
+  case NO:                                  \
+    if (env_nt) ECX_SMLAUNCH(NO, true);     \
+    else ECX_SMLAUNCH(NO, false);           \
+    break;
+    switch (l.n_out) {
+      ECX_SMDISPATCH(1)
+      ECX_SMDISPATCH(2)
+      ECX_SMDISPATCH(3)
+      ECX_SMDISPATCH(4)
+      default:
+        return ECX_ERR_INVAL;
+    }
+#undef ECX_SMDISPATCH
+#undef ECX_SMLAUNCH
+    HIP_TRY(hipGetLastError());
+    b0 += nb;
+  }
+  HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
+  s.timed = true;
+  return ECX_OK;
+}
+
+int ecx_decode_multi_plan_probe(int technique, int k, int m,
+                                const uint64_t* present_masks, long n,
+                                int* plan_of_stripe, int* n_plans) {
+  // CPU-only: the grouping the two calls above perform (same
+  // group_decode_masks, plans composed directly instead of via a context's
+  // LRU). Outputs are written only on success.
+  if (!present_masks || !plan_of_stripe || !n_plans || n <= 0 ||
+      n > 0x7fffffffL || k < 1 || m < 1 || k + m > 64)
+    return ECX_ERR_INVAL;
+  if (technique != ECX_T_RS_VAN_ISA && technique != ECX_T_CAUCHY_ISA &&
+      technique != ECX_T_RS_VAN_JERASURE)
+    return ECX_ERR_INVAL;  // w=8 matrix techniques only, like the calls
+  std::vector<uint8_t> gen;
+  if (!ecx::gen_matrix(technique, gen, k, m)) return ECX_ERR_INVAL;
+  auto resolve = [&](uint64_t mask) {
+    std::vector<int> sv, er;
+    std::vector<uint8_t> rw;
+    return ecx::compose_decode_rows(gen, k, m, mask, sv, er, rw);
+  };
+  ecx::MultiGrouping grp;
+  if (!ecx::group_decode_masks(k, m, present_masks, n, resolve, grp))
+    return ECX_ERR_IO;
+  std::memcpy(plan_of_stripe, grp.plan_of_stripe.data(), (size_t)n * 4);
+  *n_plans = (int)grp.masks.size();
+  return (int)grp.launches.size();
 }
 
 // defined in the host-pointer section below

@@ -199,6 +199,37 @@ ECX_API int ecx_decode_slices(ecx_ctx *ctx, void *const *d_chunks,
                               const size_t *bytes, int n_slices,
                               uint64_t present_mask, int slot);
 
+/* ---------------- per-stripe erasure patterns (recovery batching) --------
+ * A shim that batches degraded reads / recovery ops from many placement
+ * groups holds stripes that miss DIFFERENT chunks. These forms take one
+ * mask per stripe (per slice) instead of one per call:
+ * present_masks[s] is stripe s's mask; same layout/semantics as
+ * ecx_decode_batch applied to each stripe on its own — byte-identical
+ * result, present chunks never written, a stripe with nothing erased never
+ * touched. The number of kernel launches does not depend on how many
+ * distinct patterns the call holds and is at most m (stripes are grouped
+ * by how many chunks they lose, not by which). All validation precedes the
+ * first launch: ECX_ERR_IO if ANY mask is undecodable, ECX_ERR_INVAL for a
+ * NULL pointer, bad slot, chunk_bytes % 16, n_stripes outside 1..65535, a
+ * bitmatrix or w=16 context (as for ecx_*_slices) or, for slices, a NULL
+ * pointer for an erased chunk — in each case nothing has been launched.
+ * ecx_last_kernel_ms then covers the whole call (first launch to last). */
+ECX_API int ecx_decode_batch_multi(ecx_ctx *ctx, void *dptr, long n_stripes,
+                                   size_t chunk_bytes,
+                                   const uint64_t *present_masks, int slot);
+ECX_API int ecx_decode_slices_multi(ecx_ctx *ctx, void *const *d_chunks,
+                                    const size_t *bytes, int n_slices,
+                                    const uint64_t *present_masks, int slot);
+/* CPU-only (no GPU context): the host-side grouping the two calls above
+ * perform. plan_of_stripe[n] = index of the stripe's mask among distinct
+ * masks in first-appearance order, -1 if nothing is erased; *n_plans =
+ * number of distinct masks that erase something. Returns the number of
+ * kernel launches, or -errno (ECX_ERR_IO if any mask is undecodable;
+ * outputs are then left unwritten). */
+ECX_API int ecx_decode_multi_plan_probe(int technique, int k, int m,
+                                        const uint64_t *present_masks, long n,
+                                        int *plan_of_stripe, int *n_plans);
+
 /* Replace the coding rows of the generator with a custom m x k matrix
  * (clears decode-plan caches). Lets composed codecs — SHEC's shingled
  * matrix (src/erasure-code/shec/ErasureCodeShec.cc:700-768), custom
