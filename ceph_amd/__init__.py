@@ -111,6 +111,8 @@ def _lib():
                                      ctypes.c_int]
     lib.ecx_shec_matrix.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                     ctypes.c_int, ctypes.c_void_p]
+    lib.ecx_gf8_tabs332_probe.argtypes = [ctypes.c_uint8,
+                                          ctypes.POINTER(ctypes.c_uint32)]
     lib.ecx_sync.argtypes = [ctypes.c_void_p, ctypes.c_int]
     lib.ecx_last_kernel_ms.argtypes = [ctypes.c_void_p, ctypes.c_int,
                                        ctypes.POINTER(ctypes.c_double)]
@@ -152,6 +154,16 @@ def shec_matrix(k, m, c, single=False):
     _ck(lib().ecx_shec_matrix(k, m, c, int(single),
                               out.ctypes.data_as(ctypes.c_void_p)),
         "ecx_shec_matrix")
+    return out
+
+
+def gf8_tabs332_probe(c):
+    """CPU-only: the streaming batch kernel's five table dwords for
+    coefficient c (bit groups 0-2 / 3-5 / 6-7), as a uint32 array."""
+    out = np.zeros(5, dtype=np.uint32)
+    _ck(lib().ecx_gf8_tabs332_probe(
+        c, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))),
+        "ecx_gf8_tabs332_probe")
     return out
 
 

@@ -256,6 +256,167 @@ __global__ __launch_bounds__(256, 2) void ec_gf_matmul_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Streaming kernel for the non-accumulating batch matmul
+// (DESIGN.md §4.1). Same arithmetic as ec_gf_matmul_kernel, different
+// skeleton: every launch-uniform value (chunk offsets, coefficient classes,
+// tables) lives in a by-value argument block, so it reaches the wave through
+// scalar loads — no LDS staging, no barrier, no readfirstlane, and no
+// device-side parameter buffer for the host to upload.
+// ---------------------------------------------------------------------------
+
+#define ECX_STREAM_MAX_OUT 4
+
+struct EcStreamParams {
+  // byte offset of each source / output chunk inside a stripe
+  // (chunk id * chunk_bytes, formed on the host in 64 bits); padded because
+  // the kernel fetches offsets two sources ahead of the one it computes
+  uint64_t src_off[ECX_MAX_K + 2];
+  uint64_t out_off[ECX_STREAM_MAX_OUT];
+  // per output, one bit per source: coefficient == 1 / general coefficient
+  // (neither bit: coefficient 0 or a zeros-chunk source)
+  uint32_t one_mask[ECX_STREAM_MAX_OUT];
+  uint32_t mul_mask[ECX_STREAM_MAX_OUT];
+  // 5 dwords per (source, output), see build_tabs332(); zero where the
+  // coefficient is not a general one
+  uint32_t tabs[ECX_MAX_K][ECX_STREAM_MAX_OUT][5];
+  int n_src;
+};
+static_assert(sizeof(EcStreamParams) <= 4096,
+              "EcStreamParams must fit the kernel argument segment");
+static_assert(ECX_MAX_K <= 32, "source classes are 32-bit masks");
+
+// One source's contribution to every output accumulator. The byte is split
+// into the contiguous bit groups 0-2, 3-5, 6-7 (5 VALU per dword):
+//   c*x = A[x & 7] ^ B[(x >> 3) & 7] ^ W[x >> 6]
+template <int NOUT>
+__device__ __forceinline__ void ecx_stream_source(
+    const EcStreamParams& p, const uint32_t (&one_mask)[NOUT],
+    const uint32_t (&mul_mask)[NOUT], int i, v4u d,
+    uint32_t (&acc)[NOUT][4]) {
+  uint32_t T[NOUT][5];
+#pragma unroll
+  for (int j = 0; j < NOUT; j++)
+#pragma unroll
+    for (int q = 0; q < 5; q++) T[j][q] = p.tabs[i][j][q];
+  const uint32_t x[4] = {d.x, d.y, d.z, d.w};
+  uint32_t ia[4], ib[4], ic[4];
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    ia[q] = x[q] & 0x07070707u;
+    ib[q] = (x[q] >> 3) & 0x07070707u;
+    ic[q] = (x[q] >> 6) & 0x03030303u;
+  }
+  const uint32_t bit = 1u << i;
+#pragma unroll
+  for (int j = 0; j < NOUT; j++) {
+    // the classes merge in a 4-register term, never in the accumulators:
+    // merging acc itself makes the compiler copy all of them per source
+    uint32_t t[4];
+    if (mul_mask[j] & bit) {
+#pragma unroll
+      for (int q = 0; q < 4; q++)
+        t[q] = __builtin_amdgcn_perm(T[j][1], T[j][0], ia[q]) ^
+               __builtin_amdgcn_perm(T[j][3], T[j][2], ib[q]) ^
+               __builtin_amdgcn_perm(0u, T[j][4], ic[q]);
+    } else {
+      const uint32_t keep = (one_mask[j] & bit) ? ~0u : 0u;
+#pragma unroll
+      for (int q = 0; q < 4; q++) t[q] = x[q] & keep;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++) acc[j][q] ^= t[q];
+  }
+}
+
+// A tile is 256 lanes x 16 B of one chunk position range of one stripe.
+// Tiles are numbered outer * n_inner + inner and block b walks tiles b,
+// b + gridDim.x, ... (the grid may be anything from one block per tile to a
+// persistent one); (step_q, step_r) = divmod(gridDim.x, n_inner) from the
+// host keeps the walk free of per-tile division. stripe_fastest == 0:
+// inner = tile within the chunk, outer = stripe; 1: the other way round.
+// Register budget: 8 waves/SIMD (<= 64 VGPRs) for NOUT <= 3; NOUT = 4 needs
+// about 73 and would spill at 64, so it is asked for 6.
+template <int NOUT>
+__global__ __launch_bounds__(256, NOUT < 4 ? 8 : 6) void ec_gf_stream_kernel(
+    const uint8_t* buf, uint8_t* obuf, const EcStreamParams p,
+    uint64_t stripe_bytes, uint64_t vecs_per_chunk, uint32_t n_outer,
+    uint32_t n_inner, uint32_t step_q, uint32_t step_r, int stripe_fastest) {
+  const uint32_t voff = threadIdx.x << 4;
+  const int n_src = p.n_src;
+  uint32_t one_mask[NOUT], mul_mask[NOUT];
+#pragma unroll
+  for (int j = 0; j < NOUT; j++) {
+    one_mask[j] = p.one_mask[j];
+    mul_mask[j] = p.mul_mask[j];
+  }
+  uint32_t a = blockIdx.x / n_inner;
+  uint32_t b = blockIdx.x - a * n_inner;
+  while (a < n_outer) {
+    const uint32_t stripe = stripe_fastest ? b : a;
+    const uint32_t tile = stripe_fastest ? a : b;
+    // wave-uniform 64-bit base; the per-lane part stays a 32-bit offset
+    const uint64_t tbase =
+        (uint64_t)stripe * stripe_bytes + ((uint64_t)tile << 12);
+    if (((uint64_t)tile << 8) + threadIdx.x < vecs_per_chunk) {
+      const uint8_t* sb = buf + tbase;
+      uint32_t acc[NOUT][4];
+#pragma unroll
+      for (int j = 0; j < NOUT; j++)
+        acc[j][0] = acc[j][1] = acc[j][2] = acc[j][3] = 0u;
+      // one-ahead prefetch over two load buffers used alternately: the load
+      // of source i + 1 is in flight while source i is computed. Every load
+      // in the loop is unconditional (the last one or two sources are
+      // peeled), so each wait leaves exactly one load outstanding, and no
+      // loaded register is ever copied (a copy would wait for its load).
+      // The offset of the load after next is fetched (a scalar load) while
+      // the current one is issued, and the scheduling barrier keeps each
+      // vector load ahead of the compute it overlaps: without it the
+      // compiler hoists the compute's head above the load to cover the
+      // offset fetch, and the wait for the previous load goes with it.
+#define ECX_STREAM_LD(dst_, next_)                                        \
+  do {                                                                    \
+    dst_ = __builtin_nontemporal_load(                                    \
+        reinterpret_cast<const v4u*>(sb + so + voff));                    \
+    so = p.src_off[next_];                                                \
+    __builtin_amdgcn_sched_barrier(0);                                    \
+  } while (0)
+      uint64_t so = p.src_off[0];
+      v4u d0, d1;
+      ECX_STREAM_LD(d0, 1);
+      int i = 0;
+      for (; i + 2 < n_src; i += 2) {
+        ECX_STREAM_LD(d1, i + 2);
+        ecx_stream_source<NOUT>(p, one_mask, mul_mask, i, d0, acc);
+        ECX_STREAM_LD(d0, i + 3);  // src_off is padded: index <= n_src + 1
+        ecx_stream_source<NOUT>(p, one_mask, mul_mask, i + 1, d1, acc);
+      }
+      if (i + 1 < n_src) {
+        ECX_STREAM_LD(d1, 0);
+        ecx_stream_source<NOUT>(p, one_mask, mul_mask, i, d0, acc);
+        ecx_stream_source<NOUT>(p, one_mask, mul_mask, i + 1, d1, acc);
+      } else {
+        ecx_stream_source<NOUT>(p, one_mask, mul_mask, i, d0, acc);
+      }
+#undef ECX_STREAM_LD
+      uint8_t* ob = obuf + tbase;
+#pragma unroll
+      for (int j = 0; j < NOUT; j++) {
+        v4u o;
+        o.x = acc[j][0]; o.y = acc[j][1]; o.z = acc[j][2]; o.w = acc[j][3];
+        __builtin_nontemporal_store(
+            o, reinterpret_cast<v4u*>(ob + p.out_off[j] + voff));
+      }
+    }
+    a += step_q;
+    b += step_r;
+    if (b >= n_inner) {
+      b -= n_inner;
+      a++;
+    }
+  }
+}
+
 // Variable-size slice batch: one launch over N independent
 // slices of differing length, each with its own k+m device chunk pointers.
 // Blocks are pre-assigned (slice id, vec offset) by the host so there is no
@@ -1250,6 +1411,11 @@ struct ecx_ctx {
   // threads (the OSD's PG workers) overlap instead of serialising on one
   // stream's mutex
   std::atomic<unsigned> rr{0};
+  // grid sizing for ec_gf_stream_kernel, queried from the runtime on first
+  // use (racing callers store the same values): CU count, and resident
+  // blocks per CU for NOUT 1..4 (the persistent grid, ECX_STREAM_BPC=0)
+  std::atomic<int> stream_cus{0};
+  std::atomic<int> stream_occ[5] = {};
 
   bool is_bitmatrix() const {
     return technique == ECX_T_CAUCHY_ORIG_JERASURE ||
@@ -1504,6 +1670,21 @@ static void build_tabs(const ecx::GF8& f, uint8_t c, uint32_t* T) {
   T[5] = 0;
 }
 
+// The 5-dword v_perm tables of ec_gf_stream_kernel for one coefficient,
+// over the contiguous bit groups 0-2 / 3-5 / 6-7: T[0..1] = c*x for x in
+// 0..7, T[2..3] = c*(x<<3) for x in 0..7, T[4] = c*(x<<6) for x in 0..3.
+// GF(2^8) multiplication is linear over XOR, so the three lookups XORed
+// give c*x exactly.
+static void build_tabs332(const ecx::GF8& f, uint8_t c, uint32_t* T) {
+  for (int t = 0; t < 5; t++) T[t] = 0;
+  for (int x = 0; x < 8; x++) {
+    T[x >> 2] |= (uint32_t)f.mul(c, (uint8_t)x) << (8 * (x & 3));
+    T[2 + (x >> 2)] |= (uint32_t)f.mul(c, (uint8_t)(x << 3)) << (8 * (x & 3));
+  }
+  for (int x = 0; x < 4; x++)
+    T[4] |= (uint32_t)f.mul(c, (uint8_t)(x << 6)) << (8 * x);
+}
+
 // Populate an EcLaunchParams from a coefficient matrix (n_out x n_src over
 // source ids src_ids); src_null[i] marks zeros-chunk sources to skip
 // (the reference's zeros-buffer convention, ErasureCodeJerasure.cc:146-157).
@@ -1684,6 +1865,157 @@ static int launch_matmul(ecx_ctx* ctx, Slot& s, const uint8_t* d_buf,
   return ECX_OK;
 }
 
+// ---- streaming kernel (non-accumulating batch matmul) ----
+
+// ECX_STREAM: unset/1 = ec_gf_stream_kernel for the non-accumulating batch
+// matmul, 0 = ec_gf_matmul_kernel as before (A/B within one process lease).
+static int env_stream() {
+  static const int v = [] {
+    const char* e = getenv("ECX_STREAM");
+    return e ? atoi(e) : 1;
+  }();
+  return v;
+}
+
+// ECX_STREAM_BPC: grid size. Unset = the measured default: two tiles per
+// block, but no fewer blocks than fill the GPU (8 per CU) while tiles last
+// - at the flagship shape 524,288 blocks of two tiles. N >= 1 = N blocks
+// per CU (grid = min(tiles, CUs x N), each block grid-strides over its
+// tiles); 0 = the persistent grid, as many blocks per CU as the occupancy
+// query says stay resident. Measured at the flagship shape
+// (profiles/stream_kernel_summary.md), grids of many short blocks beat
+// every persistent grid by 4-5% on both legs.
+static int env_stream_bpc() {
+  static const int v = [] {
+    const char* e = getenv("ECX_STREAM_BPC");
+    const int x = e ? atoi(e) : -1;
+    return std::max(-1, std::min(x, 65536));
+  }();
+  return v;
+}
+
+// ECX_STREAM_ORDER: tile walk, 0/unset = tile-in-chunk fastest (concurrent
+// blocks cover a few whole stripes), 1 = stripe fastest.
+static int env_stream_order() {
+  static const int v = [] {
+    const char* e = getenv("ECX_STREAM_ORDER");
+    return e ? atoi(e) : 0;
+  }();
+  return v;
+}
+
+template <int NO>
+static hipError_t stream_occupancy(int* n) {
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      n, ec_gf_stream_kernel<NO>, 256, 0);
+}
+
+// Grid size for n_tiles tiles (see ECX_STREAM_BPC). Both runtime figures
+// (CU count, resident blocks per CU of the NOUT instance) are cached in the
+// context.
+static int stream_grid(ecx_ctx* ctx, int n_out, uint64_t n_tiles,
+                       uint32_t* grid) {
+  int cus = ctx->stream_cus.load();
+  if (cus <= 0) {
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, ctx->device));
+    cus = std::max(1, prop.multiProcessorCount);
+    ctx->stream_cus.store(cus);
+  }
+  int bpc = env_stream_bpc();
+  uint64_t g;
+  if (bpc < 0) {
+    g = std::max<uint64_t>((uint64_t)cus * 8, (n_tiles + 1) / 2);
+  } else {
+    if (bpc == 0) {
+      bpc = ctx->stream_occ[n_out].load();
+      if (bpc <= 0) {
+        hipError_t e = n_out == 1   ? stream_occupancy<1>(&bpc)
+                       : n_out == 2 ? stream_occupancy<2>(&bpc)
+                       : n_out == 3 ? stream_occupancy<3>(&bpc)
+                                    : stream_occupancy<4>(&bpc);
+        HIP_TRY(e);
+        bpc = std::max(1, bpc);
+        ctx->stream_occ[n_out].store(bpc);
+      }
+    }
+    g = (uint64_t)cus * (uint64_t)bpc;
+  }
+  // one block per tile at most, at least one block, and grid x 256 threads
+  // well inside 32 bits
+  g = std::min<uint64_t>(std::min<uint64_t>(g, n_tiles), 1ull << 23);
+  *grid = (uint32_t)std::max<uint64_t>(1, g);
+  return ECX_OK;
+}
+
+// Launch ec_gf_stream_kernel for one output group (n_out <= 4). coeff is
+// n_out x n_src. Nothing is staged on the device: the argument block is the
+// launch's own kernarg.
+static int launch_stream(ecx_ctx* ctx, Slot& s, const uint8_t* d_buf,
+                         uint8_t* d_obuf, const int* src_ids, int n_src,
+                         const int* out_ids, int n_out, const uint8_t* coeff,
+                         const bool* src_null, long n_stripes,
+                         size_t chunk_bytes, bool time_it) {
+  if (chunk_bytes % 16 || n_stripes <= 0 || n_stripes > 65535 || n_out < 1 ||
+      n_out > ECX_STREAM_MAX_OUT)
+    return ECX_ERR_INVAL;
+  HIP_TRY(hipSetDevice(ctx->device));
+
+  const ecx::GF8& f = ecx::gf8();
+  EcStreamParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.n_src = n_src;
+  for (int i = 0; i < n_src; i++)
+    p.src_off[i] = (uint64_t)src_ids[i] * chunk_bytes;
+  for (int j = 0; j < n_out; j++) {
+    p.out_off[j] = (uint64_t)out_ids[j] * chunk_bytes;
+    for (int i = 0; i < n_src; i++) {
+      const uint8_t c = coeff[(size_t)j * n_src + i];
+      if (c == 0 || (src_null && src_null[i])) continue;
+      if (c == 1) {
+        p.one_mask[j] |= 1u << i;
+      } else {
+        p.mul_mask[j] |= 1u << i;
+        build_tabs332(f, c, p.tabs[i][j]);
+      }
+    }
+  }
+
+  const uint64_t vecs = chunk_bytes >> 4;
+  const uint64_t tpc = (vecs + 255) / 256;  // tiles per chunk
+  const uint64_t n_tiles = tpc * (uint64_t)n_stripes;
+  uint32_t grid = 1;
+  int r = stream_grid(ctx, n_out, n_tiles, &grid);
+  if (r != ECX_OK) return r;
+  const int order = env_stream_order() == 1 ? 1 : 0;
+  const uint32_t n_inner =
+      (uint32_t)std::max<uint64_t>(1, order ? (uint64_t)n_stripes : tpc);
+  const uint32_t n_outer = (uint32_t)(order ? tpc : (uint64_t)n_stripes);
+  const uint32_t step_q = grid / n_inner, step_r = grid % n_inner;
+  const uint64_t stripe_bytes = (uint64_t)(ctx->k + ctx->m) * chunk_bytes;
+
+  if (time_it) HIP_TRY(hipEventRecord(s.ev_start, s.stream));
+#define ECX_STREAM_LAUNCH(NO)                                               \
+  case NO:                                                                  \
+    hipLaunchKernelGGL((ec_gf_stream_kernel<NO>), dim3(grid), dim3(256), 0, \
+                       s.stream, d_buf, d_obuf, p, stripe_bytes, vecs,      \
+                       n_outer, n_inner, step_q, step_r, order);            \
+    break;
+  switch (n_out) {
+    ECX_STREAM_LAUNCH(1)
+    ECX_STREAM_LAUNCH(2)
+    ECX_STREAM_LAUNCH(3)
+    ECX_STREAM_LAUNCH(4)
+  }
+#undef ECX_STREAM_LAUNCH
+  HIP_TRY(hipGetLastError());
+  if (time_it) {
+    HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
+    s.timed = true;
+  }
+  return ECX_OK;
+}
+
 // Run a full n_out job, splitting into groups of <= 4 outputs per launch.
 static int run_matmul(ecx_ctx* ctx, int slot_i, const uint8_t* d_buf,
                       uint8_t* d_obuf, const int* src_ids, int n_src,
@@ -1696,8 +2028,20 @@ static int run_matmul(ecx_ctx* ctx, int slot_i, const uint8_t* d_buf,
   Slot& s = ctx->slots[slot_i];
   std::lock_guard<std::recursive_mutex> g(s.mu);
   const ecx::GF8& f = ecx::gf8();
+  // non-accumulating jobs go to the streaming kernel (its tile
+  // counters are 32-bit; no real chunk comes near 2^31 tiles)
+  const bool stream = !accum && env_stream() != 0 &&
+                      (chunk_bytes >> 12) < 0x7fffffffull;
   for (int j0 = 0; j0 < n_out; j0 += 4) {
     int nj = std::min(4, n_out - j0);
+    if (stream) {
+      // rows j0..j0+nj of coeff are contiguous: n_out x n_src row-major
+      int r = launch_stream(ctx, s, d_buf, d_obuf, src_ids, n_src,
+                            out_ids + j0, nj, coeff + (size_t)j0 * n_src,
+                            src_null, n_stripes, chunk_bytes, j0 == 0);
+      if (r != ECX_OK) return r;
+      continue;
+    }
     EcLaunchParams p;
     std::vector<uint8_t> sub((size_t)nj * n_src);
     for (int j = 0; j < nj; j++)
@@ -2816,6 +3160,12 @@ int ecx_shec_matrix(int k, int m, int c, int single, uint8_t* out) {
   std::vector<uint8_t> coding;
   if (!ecx::shec_matrix(coding, k, m, c, single != 0)) return ECX_ERR_INVAL;
   std::memcpy(out, coding.data(), coding.size());
+  return ECX_OK;
+}
+
+int ecx_gf8_tabs332_probe(uint8_t c, uint32_t out[5]) {
+  if (!out) return ECX_ERR_INVAL;
+  build_tabs332(ecx::gf8(), c, out);
   return ECX_OK;
 }
 

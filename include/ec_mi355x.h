@@ -262,6 +262,12 @@ ECX_API int ecx_decode_rows_probe(int technique, int k, int m,
                                   uint64_t present_mask, int *survivors,
                                   int *erased, uint8_t *rows);
 
+/* CPU-only probe of the streaming batch kernel's table builder: the five
+ * v_perm table dwords for coefficient c over the bit groups 0-2 / 3-5 / 6-7.
+ * Byte x&7 of {out[0], out[1]} ^ byte (x>>3)&7 of {out[2], out[3]} ^ byte
+ * x>>6 of out[4] (little-endian byte order) is c*x in GF(2^8). */
+ECX_API int ecx_gf8_tabs332_probe(uint8_t c, uint32_t out[5]);
+
 /* Generic device-batch GF(2^8) matmul over the standard batch layout:
  * out chunk ids = XOR_i rows[j*n_src+i] * src chunk ids, per stripe. The
  * composition primitive for layered codes (LRC layers, custom research
