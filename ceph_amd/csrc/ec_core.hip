@@ -42,6 +42,7 @@
 #include <thread>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ec_mi355x.h"
@@ -85,28 +86,16 @@ __device__ __forceinline__ uint32_t ecx_gfmul4(uint32_t l0, uint32_t l1,
          __builtin_amdgcn_perm(0u, w, i8);
 }
 
-// VPT = 16-byte vectors per thread per grid-stride iteration. VPT=2 gives
-// each lane two independent load/accumulate chains (more memory-level
-// parallelism, half the loop overhead); both vectors of a lane are
-// blockDim.x apart so every wave access stays a fully coalesced 1 KiB
-// transaction.
-// KN > 0 statically unrolls the source loop (flagship k=8): all k loads
-// are grouped ahead of the compute within a position, deepening MLP.
-// PF: source prefetch depth — issue source i+PF's load before computing
-// on source i, so each wave keeps PF loads in flight across the compute
-// body (the dynamic i-loop otherwise serialises load -> use). Costs
-// PF*VPT*4 VGPRs; targeted at the NOUT=4 shapes where the all-ones
-// probe measured 15-20% of wall as VALU not hidden behind the stream.
-template <int NOUT, bool ACCUM, int VPT, bool NT, int KN = 0, int PF = 0>
-__global__ __launch_bounds__(256, 2) void ec_gf_matmul_kernel(
-    const uint8_t* __restrict__ buf, uint8_t* __restrict__ obuf,
-    const EcLaunchParams* __restrict__ pb, long chunk_bytes,
-    int chunks_per_stripe, long vecs_per_chunk) {
-  __shared__ uint32_t s_tabs[ECX_MAX_OUT * ECX_MAX_K * 6];
-  __shared__ int s_src[ECX_MAX_K];
-  __shared__ int s_out[ECX_MAX_OUT];
-  __shared__ uint8_t s_cls[ECX_MAX_OUT * ECX_MAX_K];
-  const int n_src = KN ? KN : pb->n_src;
+// ---- shared pieces of the four table kernels (ec_gf_matmul_kernel,
+// ec_gf_slices_kernel and their *_multi forms) ----
+
+// Stage one launch record into the kernel's own LDS arrays. Rec is
+// EcLaunchParams or EcMultiRec (same field names, different capacities).
+template <int NOUT, class Rec>
+__device__ __forceinline__ void ecx_stage_rec(const Rec* __restrict__ pb,
+                                              int n_src, uint32_t* s_tabs,
+                                              int* s_src, int* s_out,
+                                              uint8_t* s_cls) {
   for (int t = threadIdx.x; t < NOUT * n_src * 6; t += blockDim.x)
     s_tabs[t] = pb->tabs[t];
   for (int t = threadIdx.x; t < n_src; t += blockDim.x)
@@ -116,144 +105,118 @@ __global__ __launch_bounds__(256, 2) void ec_gf_matmul_kernel(
   for (int t = threadIdx.x; t < NOUT * n_src; t += blockDim.x)
     s_cls[t] = pb->cls[t];
   __syncthreads();
+}
 
-  const long stripe = blockIdx.y;
-  const uint8_t* sbase = buf + stripe * chunks_per_stripe * chunk_bytes;
-  uint8_t* obase = obuf + stripe * chunks_per_stripe * chunk_bytes;
+template <bool NT>
+__device__ __forceinline__ v4u ecx_ld16(const uint8_t* p) {
+  const v4u* p4 = reinterpret_cast<const v4u*>(p);
+  return NT ? __builtin_nontemporal_load(p4) : *p4;
+}
 
-  for (long p0 = (long)blockIdx.x * blockDim.x * VPT + threadIdx.x;
-       p0 < vecs_per_chunk; p0 += (long)gridDim.x * blockDim.x * VPT) {
-    long off[VPT];
-    bool live[VPT];
-#pragma unroll
-    for (int v = 0; v < VPT; v++) {
-      long p = p0 + (long)v * blockDim.x;
-      live[v] = p < vecs_per_chunk;
-      off[v] = p << 4;
-    }
-    uint32_t acc[NOUT][VPT][4];
-#pragma unroll
-    for (int j = 0; j < NOUT; j++)
-#pragma unroll
-      for (int v = 0; v < VPT; v++) {
-        if (ACCUM && live[v]) {
-          const v4u o = *reinterpret_cast<const v4u*>(
-              obase + (long)s_out[j] * chunk_bytes + off[v]);
-          acc[j][v][0] = o.x; acc[j][v][1] = o.y;
-          acc[j][v][2] = o.z; acc[j][v][3] = o.w;
-        } else {
-          acc[j][v][0] = acc[j][v][1] = acc[j][v][2] = acc[j][v][3] = 0u;
-        }
-      }
+template <bool NT>
+__device__ __forceinline__ void ecx_st16(uint8_t* p, v4u o) {
+  v4u* p4 = reinterpret_cast<v4u*>(p);
+  if (NT)
+    __builtin_nontemporal_store(o, p4);
+  else
+    *p4 = o;
+}
 
-    uint32_t dnf[PF ? PF : 1][VPT][4];
+// One source vector into one output's accumulator by its class: 0 skip,
+// 1 XOR, 2 table multiply. The accumulator goes in and out by value and is
+// only ever touched whole: behind a reference, or updated dword by dword,
+// the compiler fuses all NOUT of them into one wide vector that it copies
+// at every class branch (+5 to +15 VGPRs at NOUT >= 3).
+__device__ __forceinline__ v4u ecx_gf_out(int cls, const uint32_t* T, v4u d,
+                                          v4u i7l, v4u i7h, v4u i8, v4u a) {
+  if (cls == 1) {
+    a ^= d;
+  } else if (cls != 0) {
+    const uint32_t l0 = T[0], l1 = T[1], h0 = T[2], h1 = T[3], w8 = T[4];
+    v4u t;
 #pragma unroll
-    for (int pd = 0; pd < PF; pd++) {
-      const int si = pd < n_src ? pd : n_src - 1;
-      const uint8_t* sp0 = sbase + (long)s_src[si] * chunk_bytes;
-#pragma unroll
-      for (int v = 0; v < VPT; v++) {
-        v4u d = {0, 0, 0, 0};
-        if (live[v]) {
-          const v4u* p4 = reinterpret_cast<const v4u*>(sp0 + off[v]);
-          d = NT ? __builtin_nontemporal_load(p4) : *p4;
-        }
-        dnf[pd][v][0] = d.x; dnf[pd][v][1] = d.y;
-        dnf[pd][v][2] = d.z; dnf[pd][v][3] = d.w;
-      }
-    }
-#pragma unroll (KN ? KN : 1)
-    for (int i = 0; i < n_src; i++) {
-      const uint8_t* sp = sbase + (long)s_src[i] * chunk_bytes;
-      uint32_t dq[VPT][4];
-      uint32_t i7l[VPT][4], i7h[VPT][4], i8[VPT][4];
-#pragma unroll
-      for (int v = 0; v < VPT; v++) {
-        v4u d = {0, 0, 0, 0};
-        if (PF) {
-          d.x = dnf[0][v][0]; d.y = dnf[0][v][1];
-          d.z = dnf[0][v][2]; d.w = dnf[0][v][3];
-        } else if (live[v]) {
-          const v4u* p4 = reinterpret_cast<const v4u*>(sp + off[v]);
-          d = NT ? __builtin_nontemporal_load(p4) : *p4;
-        }
-        dq[v][0] = d.x; dq[v][1] = d.y; dq[v][2] = d.z; dq[v][3] = d.w;
-      }
-      if (PF) {
-        // rotate the prefetch ring and issue source i+PF
-#pragma unroll
-        for (int pd = 0; pd + 1 < PF; pd++)
-#pragma unroll
-          for (int v = 0; v < VPT; v++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) dnf[pd][v][q] = dnf[pd + 1][v][q];
-        if (i + PF < n_src) {
-          const uint8_t* spn = sbase + (long)s_src[i + PF] * chunk_bytes;
-#pragma unroll
-          for (int v = 0; v < VPT; v++) {
-            v4u d = {0, 0, 0, 0};
-            if (live[v]) {
-              const v4u* p4 = reinterpret_cast<const v4u*>(spn + off[v]);
-              d = NT ? __builtin_nontemporal_load(p4) : *p4;
-            }
-            dnf[PF ? PF - 1 : 0][v][0] = d.x;
-            dnf[PF ? PF - 1 : 0][v][1] = d.y;
-            dnf[PF ? PF - 1 : 0][v][2] = d.z;
-            dnf[PF ? PF - 1 : 0][v][3] = d.w;
-          }
-        }
-      }
-#pragma unroll
-      for (int v = 0; v < VPT; v++) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          i7l[v][q] = dq[v][q] & 0x07070707u;
-          i7h[v][q] = (dq[v][q] >> 4) & 0x07070707u;
-          i8[v][q] = ((dq[v][q] >> 3) & 0x01010101u) |
-                     ((dq[v][q] >> 6) & 0x02020202u);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < NOUT; j++) {
-        // cls is uniform across the wave; readfirstlane makes the branch a
-        // scalar s_cbranch instead of an exec-mask dance
-        const int cls = __builtin_amdgcn_readfirstlane(s_cls[j * n_src + i]);
-        if (cls == 0) continue;
-        if (cls == 1) {
-#pragma unroll
-          for (int v = 0; v < VPT; v++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) acc[j][v][q] ^= dq[v][q];
-        } else {
-          const uint32_t* T = &s_tabs[(j * n_src + i) * 6];
-          const uint32_t l0 = T[0], l1 = T[1], h0 = T[2], h1 = T[3],
-                         w8 = T[4];
-#pragma unroll
-          for (int v = 0; v < VPT; v++)
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-              acc[j][v][q] ^= ecx_gfmul4(l0, l1, h0, h1, w8, i7l[v][q],
-                                         i7h[v][q], i8[v][q]);
-        }
-      }
-    }
-
-#pragma unroll
-    for (int j = 0; j < NOUT; j++)
-#pragma unroll
-      for (int v = 0; v < VPT; v++) {
-        if (!live[v]) continue;
-        v4u o;
-        o.x = acc[j][v][0]; o.y = acc[j][v][1];
-        o.z = acc[j][v][2]; o.w = acc[j][v][3];
-        v4u* p4 = reinterpret_cast<v4u*>(obase + (long)s_out[j] * chunk_bytes +
-                                         off[v]);
-        if (NT)
-          __builtin_nontemporal_store(o, p4);
-        else
-          *p4 = o;
-      }
+    for (int q = 0; q < 4; q++)
+      t[q] = ecx_gfmul4(l0, l1, h0, h1, w8, i7l[q], i7h[q], i8[q]);
+    a ^= t;
   }
+  return a;
+}
+
+// Source i's 16 B vector d into all NOUT accumulators: the index split of
+// ecx_gfmul4 once per source, then ecx_gf_out per output.
+template <int NOUT>
+__device__ __forceinline__ void ecx_gf_source(const uint32_t* s_tabs,
+                                              const uint8_t* s_cls, int n_src,
+                                              int i, v4u d,
+                                              v4u (&acc)[NOUT]) {
+  const v4u i7l = d & 0x07070707u, i7h = (d >> 4) & 0x07070707u;
+  const v4u i8 = ((d >> 3) & 0x01010101u) | ((d >> 6) & 0x02020202u);
+#pragma unroll
+  for (int j = 0; j < NOUT; j++)
+    // cls is uniform across the wave (one record per block); readfirstlane
+    // makes the branch a scalar s_cbranch instead of an exec-mask dance
+    acc[j] = ecx_gf_out(__builtin_amdgcn_readfirstlane(s_cls[j * n_src + i]),
+                        &s_tabs[(j * n_src + i) * 6], d, i7l, i7h, i8, acc[j]);
+}
+
+// Contiguous-batch body: one stripe (sbase/obase), grid-stride over its
+// 16 B positions. PF = 1: one-ahead source prefetch — source i+1's load is
+// issued before computing on source i, so each wave keeps a load in flight
+// across the compute body (the i-loop otherwise serialises load -> use).
+// Costs 4 VGPRs; targeted at the NOUT=4 shapes where the all-ones probe
+// measured 15-20% of wall as VALU not hidden behind the stream. nthr is
+// blockDim.x, read by the kernel ahead of the staging barrier (read here it
+// costs a second, per-lane fetch after the barrier).
+template <int NOUT, bool ACCUM, bool NT, int PF>
+__device__ __forceinline__ void ecx_batch_body(
+    const uint8_t* __restrict__ sbase, uint8_t* __restrict__ obase,
+    long chunk_bytes, long vecs_per_chunk, int n_src, unsigned nthr,
+    const uint32_t* s_tabs, const int* s_src, const int* s_out,
+    const uint8_t* s_cls) {
+  for (long p = (long)blockIdx.x * nthr + threadIdx.x; p < vecs_per_chunk;
+       p += (long)gridDim.x * nthr) {
+    const long off = p << 4;
+    v4u acc[NOUT];
+#pragma unroll
+    for (int j = 0; j < NOUT; j++)
+      acc[j] = ACCUM ? *reinterpret_cast<const v4u*>(
+                           obase + (long)s_out[j] * chunk_bytes + off)
+                     : v4u{0, 0, 0, 0};
+    v4u nxt = {0, 0, 0, 0};
+    if (PF) nxt = ecx_ld16<NT>(sbase + (long)s_src[0] * chunk_bytes + off);
+    for (int i = 0; i < n_src; i++) {
+      v4u d;
+      if (PF) {
+        d = nxt;
+        if (i + 1 < n_src)
+          nxt = ecx_ld16<NT>(sbase + (long)s_src[i + 1] * chunk_bytes + off);
+      } else {
+        d = ecx_ld16<NT>(sbase + (long)s_src[i] * chunk_bytes + off);
+      }
+      ecx_gf_source<NOUT>(s_tabs, s_cls, n_src, i, d, acc);
+    }
+#pragma unroll
+    for (int j = 0; j < NOUT; j++)
+      ecx_st16<NT>(obase + (long)s_out[j] * chunk_bytes + off, acc[j]);
+  }
+}
+
+template <int NOUT, bool ACCUM, bool NT, int PF>
+__global__ __launch_bounds__(256, 2) void ec_gf_matmul_kernel(
+    const uint8_t* __restrict__ buf, uint8_t* __restrict__ obuf,
+    const EcLaunchParams* __restrict__ pb, long chunk_bytes,
+    int chunks_per_stripe, long vecs_per_chunk) {
+  __shared__ uint32_t s_tabs[ECX_MAX_OUT * ECX_MAX_K * 6];
+  __shared__ int s_src[ECX_MAX_K];
+  __shared__ int s_out[ECX_MAX_OUT];
+  __shared__ uint8_t s_cls[ECX_MAX_OUT * ECX_MAX_K];
+  const int n_src = pb->n_src;
+  const unsigned nthr = blockDim.x;
+  ecx_stage_rec<NOUT>(pb, n_src, s_tabs, s_src, s_out, s_cls);
+  const long sbytes = (long)blockIdx.y * chunks_per_stripe * chunk_bytes;
+  ecx_batch_body<NOUT, ACCUM, NT, PF>(buf + sbytes, obuf + sbytes,
+                                      chunk_bytes, vecs_per_chunk, n_src, nthr,
+                                      s_tabs, s_src, s_out, s_cls);
 }
 
 // ---------------------------------------------------------------------------
@@ -423,6 +386,36 @@ __global__ __launch_bounds__(256, NOUT < 4 ? 8 : 6) void ec_gf_stream_kernel(
 // per-thread search; a NULL data pointer means a zeros chunk for that slice
 // only (wave-uniform skip).
 template <int NOUT, bool NT>
+__device__ __forceinline__ void ecx_slices_body(
+    const uint64_t* __restrict__ chunk_ptrs,
+    const int* __restrict__ block_slice, const long* __restrict__ block_voff,
+    const long* __restrict__ slice_vecs, int cps, int vecs_per_block,
+    int n_src, const uint32_t* s_tabs, const int* s_src, const int* s_out,
+    const uint8_t* s_cls) {
+  const int sl = block_slice[blockIdx.x];
+  const long v0 = block_voff[blockIdx.x];
+  const long nv = slice_vecs[sl];
+  const long vend = v0 + vecs_per_block < nv ? v0 + vecs_per_block : nv;
+  const uint64_t* ptrs = chunk_ptrs + (long)sl * cps;
+
+  for (long p = v0 + threadIdx.x; p < vend; p += blockDim.x) {
+    const long off = p << 4;
+    v4u acc[NOUT];
+#pragma unroll
+    for (int j = 0; j < NOUT; j++) acc[j] = v4u{0, 0, 0, 0};
+    for (int i = 0; i < n_src; i++) {
+      const uint8_t* sp = (const uint8_t*)ptrs[s_src[i]];
+      if (sp == nullptr) continue;  // zeros chunk for this slice
+      ecx_gf_source<NOUT>(s_tabs, s_cls, n_src, i, ecx_ld16<NT>(sp + off),
+                          acc);
+    }
+#pragma unroll
+    for (int j = 0; j < NOUT; j++)
+      ecx_st16<NT>((uint8_t*)ptrs[s_out[j]] + off, acc[j]);
+  }
+}
+
+template <int NOUT, bool NT>
 __global__ __launch_bounds__(256, 2) void ec_gf_slices_kernel(
     const uint64_t* __restrict__ chunk_ptrs,  // [n_slices * cps]
     const int* __restrict__ block_slice,      // [gridDim.x]
@@ -434,73 +427,10 @@ __global__ __launch_bounds__(256, 2) void ec_gf_slices_kernel(
   __shared__ int s_out[ECX_MAX_OUT];
   __shared__ uint8_t s_cls[ECX_MAX_OUT * ECX_MAX_K];
   const int n_src = pb->n_src;
-  for (int t = threadIdx.x; t < NOUT * n_src * 6; t += blockDim.x)
-    s_tabs[t] = pb->tabs[t];
-  for (int t = threadIdx.x; t < n_src; t += blockDim.x)
-    s_src[t] = pb->src_ids[t];
-  for (int t = threadIdx.x; t < NOUT; t += blockDim.x)
-    s_out[t] = pb->out_ids[t];
-  for (int t = threadIdx.x; t < NOUT * n_src; t += blockDim.x)
-    s_cls[t] = pb->cls[t];
-  __syncthreads();
-
-  const int sl = block_slice[blockIdx.x];
-  const long v0 = block_voff[blockIdx.x];
-  const long nv = slice_vecs[sl];
-  const long vend = v0 + vecs_per_block < nv ? v0 + vecs_per_block : nv;
-  const uint64_t* ptrs = chunk_ptrs + (long)sl * cps;
-
-  for (long p = v0 + threadIdx.x; p < vend; p += blockDim.x) {
-    const long off = p << 4;
-    uint32_t acc[NOUT][4];
-#pragma unroll
-    for (int j = 0; j < NOUT; j++)
-      acc[j][0] = acc[j][1] = acc[j][2] = acc[j][3] = 0u;
-
-    for (int i = 0; i < n_src; i++) {
-      const uint8_t* sp = (const uint8_t*)ptrs[s_src[i]];
-      if (sp == nullptr) continue;  // zeros chunk for this slice
-      const v4u* p4 = reinterpret_cast<const v4u*>(sp + off);
-      const v4u d = NT ? __builtin_nontemporal_load(p4) : *p4;
-      const uint32_t dq[4] = {d.x, d.y, d.z, d.w};
-      uint32_t i7l[4], i7h[4], i8[4];
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        i7l[q] = dq[q] & 0x07070707u;
-        i7h[q] = (dq[q] >> 4) & 0x07070707u;
-        i8[q] = ((dq[q] >> 3) & 0x01010101u) |
-                ((dq[q] >> 6) & 0x02020202u);
-      }
-#pragma unroll
-      for (int j = 0; j < NOUT; j++) {
-        const int cls = __builtin_amdgcn_readfirstlane(s_cls[j * n_src + i]);
-        if (cls == 0) continue;
-        if (cls == 1) {
-#pragma unroll
-          for (int q = 0; q < 4; q++) acc[j][q] ^= dq[q];
-        } else {
-          const uint32_t* T = &s_tabs[(j * n_src + i) * 6];
-          const uint32_t l0 = T[0], l1 = T[1], h0 = T[2], h1 = T[3],
-                         w8 = T[4];
-#pragma unroll
-          for (int q = 0; q < 4; q++)
-            acc[j][q] ^= ecx_gfmul4(l0, l1, h0, h1, w8, i7l[q], i7h[q],
-                                    i8[q]);
-        }
-      }
-    }
-
-#pragma unroll
-    for (int j = 0; j < NOUT; j++) {
-      v4u o;
-      o.x = acc[j][0]; o.y = acc[j][1]; o.z = acc[j][2]; o.w = acc[j][3];
-      v4u* p4 = reinterpret_cast<v4u*>((uint8_t*)ptrs[s_out[j]] + off);
-      if (NT)
-        __builtin_nontemporal_store(o, p4);
-      else
-        *p4 = o;
-    }
-  }
+  ecx_stage_rec<NOUT>(pb, n_src, s_tabs, s_src, s_out, s_cls);
+  ecx_slices_body<NOUT, NT>(chunk_ptrs, block_slice, block_voff, slice_vecs,
+                            cps, vecs_per_block, n_src, s_tabs, s_src, s_out,
+                            s_cls);
 }
 
 // ---- per-stripe erasure patterns (ecx_decode_*_multi) ----
@@ -525,12 +455,10 @@ struct EcMultiRec {
   uint32_t tabs[ECX_MULTI_OUT * ECX_MAX_K * 6];  // [(j * n_src + i) * 6]
 };
 
-// Body is ec_gf_matmul_kernel's (ACCUM = false, KN = 0) — kept as a separate
-// kernel so the uniform-pattern instances the flagship numbers rest on are
-// compiled from untouched source. Decode is in place: sources (survivors)
-// and outputs (erased) of a stripe are disjoint chunks, so buf/obuf may
-// both be __restrict__ and passes of one stripe do not interfere.
-template <int NOUT, int VPT, bool NT, int PF>
+// Decode is in place: sources (survivors) and outputs (erased) of a stripe
+// are disjoint chunks, so buf/obuf may both be __restrict__ and passes of
+// one stripe do not interfere.
+template <int NOUT, bool NT, int PF>
 __global__ __launch_bounds__(256, 2) void ec_gf_matmul_multi_kernel(
     const uint8_t* __restrict__ buf, uint8_t* __restrict__ obuf,
     const EcMultiRec* __restrict__ recs,       // [n_plans * n_pass]
@@ -543,144 +471,13 @@ __global__ __launch_bounds__(256, 2) void ec_gf_matmul_multi_kernel(
   __shared__ int s_out[ECX_MULTI_OUT];
   __shared__ uint8_t s_cls[ECX_MULTI_OUT * ECX_MAX_K];
   const long stripe = stripe_list[blockIdx.y];
-  const EcMultiRec* pb =
-      recs + ((long)plan_of_stripe[stripe] * n_pass + pass);
-  for (int t = threadIdx.x; t < NOUT * n_src * 6; t += blockDim.x)
-    s_tabs[t] = pb->tabs[t];
-  for (int t = threadIdx.x; t < n_src; t += blockDim.x)
-    s_src[t] = pb->src_ids[t];
-  for (int t = threadIdx.x; t < NOUT; t += blockDim.x)
-    s_out[t] = pb->out_ids[t];
-  for (int t = threadIdx.x; t < NOUT * n_src; t += blockDim.x)
-    s_cls[t] = pb->cls[t];
-  __syncthreads();
-
-  const uint8_t* sbase = buf + stripe * chunks_per_stripe * chunk_bytes;
-  uint8_t* obase = obuf + stripe * chunks_per_stripe * chunk_bytes;
-
-  for (long p0 = (long)blockIdx.x * blockDim.x * VPT + threadIdx.x;
-       p0 < vecs_per_chunk; p0 += (long)gridDim.x * blockDim.x * VPT) {
-    long off[VPT];
-    bool live[VPT];
-#pragma unroll
-    for (int v = 0; v < VPT; v++) {
-      long p = p0 + (long)v * blockDim.x;
-      live[v] = p < vecs_per_chunk;
-      off[v] = p << 4;
-    }
-    uint32_t acc[NOUT][VPT][4];
-#pragma unroll
-    for (int j = 0; j < NOUT; j++)
-#pragma unroll
-      for (int v = 0; v < VPT; v++)
-        acc[j][v][0] = acc[j][v][1] = acc[j][v][2] = acc[j][v][3] = 0u;
-
-    uint32_t dnf[PF ? PF : 1][VPT][4];
-#pragma unroll
-    for (int pd = 0; pd < PF; pd++) {
-      const int si = pd < n_src ? pd : n_src - 1;
-      const uint8_t* sp0 = sbase + (long)s_src[si] * chunk_bytes;
-#pragma unroll
-      for (int v = 0; v < VPT; v++) {
-        v4u d = {0, 0, 0, 0};
-        if (live[v]) {
-          const v4u* p4 = reinterpret_cast<const v4u*>(sp0 + off[v]);
-          d = NT ? __builtin_nontemporal_load(p4) : *p4;
-        }
-        dnf[pd][v][0] = d.x; dnf[pd][v][1] = d.y;
-        dnf[pd][v][2] = d.z; dnf[pd][v][3] = d.w;
-      }
-    }
-    for (int i = 0; i < n_src; i++) {
-      const uint8_t* sp = sbase + (long)s_src[i] * chunk_bytes;
-      uint32_t dq[VPT][4];
-      uint32_t i7l[VPT][4], i7h[VPT][4], i8[VPT][4];
-#pragma unroll
-      for (int v = 0; v < VPT; v++) {
-        v4u d = {0, 0, 0, 0};
-        if (PF) {
-          d.x = dnf[0][v][0]; d.y = dnf[0][v][1];
-          d.z = dnf[0][v][2]; d.w = dnf[0][v][3];
-        } else if (live[v]) {
-          const v4u* p4 = reinterpret_cast<const v4u*>(sp + off[v]);
-          d = NT ? __builtin_nontemporal_load(p4) : *p4;
-        }
-        dq[v][0] = d.x; dq[v][1] = d.y; dq[v][2] = d.z; dq[v][3] = d.w;
-      }
-      if (PF) {
-        // rotate the prefetch ring and issue source i+PF
-#pragma unroll
-        for (int pd = 0; pd + 1 < PF; pd++)
-#pragma unroll
-          for (int v = 0; v < VPT; v++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) dnf[pd][v][q] = dnf[pd + 1][v][q];
-        if (i + PF < n_src) {
-          const uint8_t* spn = sbase + (long)s_src[i + PF] * chunk_bytes;
-#pragma unroll
-          for (int v = 0; v < VPT; v++) {
-            v4u d = {0, 0, 0, 0};
-            if (live[v]) {
-              const v4u* p4 = reinterpret_cast<const v4u*>(spn + off[v]);
-              d = NT ? __builtin_nontemporal_load(p4) : *p4;
-            }
-            dnf[PF ? PF - 1 : 0][v][0] = d.x;
-            dnf[PF ? PF - 1 : 0][v][1] = d.y;
-            dnf[PF ? PF - 1 : 0][v][2] = d.z;
-            dnf[PF ? PF - 1 : 0][v][3] = d.w;
-          }
-        }
-      }
-#pragma unroll
-      for (int v = 0; v < VPT; v++) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          i7l[v][q] = dq[v][q] & 0x07070707u;
-          i7h[v][q] = (dq[v][q] >> 4) & 0x07070707u;
-          i8[v][q] = ((dq[v][q] >> 3) & 0x01010101u) |
-                     ((dq[v][q] >> 6) & 0x02020202u);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < NOUT; j++) {
-        // uniform across the wave (one record per block): scalar branch
-        const int cls = __builtin_amdgcn_readfirstlane(s_cls[j * n_src + i]);
-        if (cls == 0) continue;
-        if (cls == 1) {
-#pragma unroll
-          for (int v = 0; v < VPT; v++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) acc[j][v][q] ^= dq[v][q];
-        } else {
-          const uint32_t* T = &s_tabs[(j * n_src + i) * 6];
-          const uint32_t l0 = T[0], l1 = T[1], h0 = T[2], h1 = T[3],
-                         w8 = T[4];
-#pragma unroll
-          for (int v = 0; v < VPT; v++)
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-              acc[j][v][q] ^= ecx_gfmul4(l0, l1, h0, h1, w8, i7l[v][q],
-                                         i7h[v][q], i8[v][q]);
-        }
-      }
-    }
-
-#pragma unroll
-    for (int j = 0; j < NOUT; j++)
-#pragma unroll
-      for (int v = 0; v < VPT; v++) {
-        if (!live[v]) continue;
-        v4u o;
-        o.x = acc[j][v][0]; o.y = acc[j][v][1];
-        o.z = acc[j][v][2]; o.w = acc[j][v][3];
-        v4u* p4 = reinterpret_cast<v4u*>(obase + (long)s_out[j] * chunk_bytes +
-                                         off[v]);
-        if (NT)
-          __builtin_nontemporal_store(o, p4);
-        else
-          *p4 = o;
-      }
-  }
+  const unsigned nthr = blockDim.x;
+  ecx_stage_rec<NOUT>(recs + ((long)plan_of_stripe[stripe] * n_pass + pass),
+                      n_src, s_tabs, s_src, s_out, s_cls);
+  const long sbytes = stripe * chunks_per_stripe * chunk_bytes;
+  ecx_batch_body<NOUT, false, NT, PF>(buf + sbytes, obuf + sbytes,
+                                      chunk_bytes, vecs_per_chunk, n_src, nthr,
+                                      s_tabs, s_src, s_out, s_cls);
 }
 
 // Slices form: the per-block (slice, voff) table gains the record index;
@@ -699,74 +496,11 @@ __global__ __launch_bounds__(256, 2) void ec_gf_slices_multi_kernel(
   __shared__ int s_src[ECX_MAX_K];
   __shared__ int s_out[ECX_MULTI_OUT];
   __shared__ uint8_t s_cls[ECX_MULTI_OUT * ECX_MAX_K];
-  const EcMultiRec* pb = recs + block_rec[blockIdx.x];
-  for (int t = threadIdx.x; t < NOUT * n_src * 6; t += blockDim.x)
-    s_tabs[t] = pb->tabs[t];
-  for (int t = threadIdx.x; t < n_src; t += blockDim.x)
-    s_src[t] = pb->src_ids[t];
-  for (int t = threadIdx.x; t < NOUT; t += blockDim.x)
-    s_out[t] = pb->out_ids[t];
-  for (int t = threadIdx.x; t < NOUT * n_src; t += blockDim.x)
-    s_cls[t] = pb->cls[t];
-  __syncthreads();
-
-  const int sl = block_slice[blockIdx.x];
-  const long v0 = block_voff[blockIdx.x];
-  const long nv = slice_vecs[sl];
-  const long vend = v0 + vecs_per_block < nv ? v0 + vecs_per_block : nv;
-  const uint64_t* ptrs = chunk_ptrs + (long)sl * cps;
-
-  for (long p = v0 + threadIdx.x; p < vend; p += blockDim.x) {
-    const long off = p << 4;
-    uint32_t acc[NOUT][4];
-#pragma unroll
-    for (int j = 0; j < NOUT; j++)
-      acc[j][0] = acc[j][1] = acc[j][2] = acc[j][3] = 0u;
-
-    for (int i = 0; i < n_src; i++) {
-      const uint8_t* sp = (const uint8_t*)ptrs[s_src[i]];
-      if (sp == nullptr) continue;  // zeros chunk for this slice
-      const v4u* p4 = reinterpret_cast<const v4u*>(sp + off);
-      const v4u d = NT ? __builtin_nontemporal_load(p4) : *p4;
-      const uint32_t dq[4] = {d.x, d.y, d.z, d.w};
-      uint32_t i7l[4], i7h[4], i8[4];
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        i7l[q] = dq[q] & 0x07070707u;
-        i7h[q] = (dq[q] >> 4) & 0x07070707u;
-        i8[q] = ((dq[q] >> 3) & 0x01010101u) |
-                ((dq[q] >> 6) & 0x02020202u);
-      }
-#pragma unroll
-      for (int j = 0; j < NOUT; j++) {
-        const int cls = __builtin_amdgcn_readfirstlane(s_cls[j * n_src + i]);
-        if (cls == 0) continue;
-        if (cls == 1) {
-#pragma unroll
-          for (int q = 0; q < 4; q++) acc[j][q] ^= dq[q];
-        } else {
-          const uint32_t* T = &s_tabs[(j * n_src + i) * 6];
-          const uint32_t l0 = T[0], l1 = T[1], h0 = T[2], h1 = T[3],
-                         w8 = T[4];
-#pragma unroll
-          for (int q = 0; q < 4; q++)
-            acc[j][q] ^= ecx_gfmul4(l0, l1, h0, h1, w8, i7l[q], i7h[q],
-                                    i8[q]);
-        }
-      }
-    }
-
-#pragma unroll
-    for (int j = 0; j < NOUT; j++) {
-      v4u o;
-      o.x = acc[j][0]; o.y = acc[j][1]; o.z = acc[j][2]; o.w = acc[j][3];
-      v4u* p4 = reinterpret_cast<v4u*>((uint8_t*)ptrs[s_out[j]] + off);
-      if (NT)
-        __builtin_nontemporal_store(o, p4);
-      else
-        *p4 = o;
-    }
-  }
+  ecx_stage_rec<NOUT>(recs + block_rec[blockIdx.x], n_src, s_tabs, s_src,
+                      s_out, s_cls);
+  ecx_slices_body<NOUT, NT>(chunk_ptrs, block_slice, block_voff, slice_vecs,
+                            cps, vecs_per_block, n_src, s_tabs, s_src, s_out,
+                            s_cls);
 }
 
 // ---- GF(2^16) (w=16 jerasure RS-van) path ----
@@ -1685,15 +1419,16 @@ static void build_tabs332(const ecx::GF8& f, uint8_t c, uint32_t* T) {
     T[4] |= (uint32_t)f.mul(c, (uint8_t)(x << 6)) << (8 * x);
 }
 
-// Populate an EcLaunchParams from a coefficient matrix (n_out x n_src over
-// source ids src_ids); src_null[i] marks zeros-chunk sources to skip
-// (the reference's zeros-buffer convention, ErasureCodeJerasure.cc:146-157).
-static void fill_params(EcLaunchParams* p, const ecx::GF8& f,
-                        const int* src_ids, int n_src, const int* out_ids,
-                        int n_out, const uint8_t* coeff /* n_out x n_src */,
-                        const bool* src_null) {
-  p->n_src = n_src;
-  p->n_out = n_out;
+// Fill the fields EcLaunchParams and EcMultiRec share from a coefficient
+// matrix (n_out x n_src over source ids src_ids); src_null[i] marks
+// zeros-chunk sources to skip (the reference's zeros-buffer convention,
+// ErasureCodeJerasure.cc:146-157).
+template <class Rec>
+static void fill_rec(Rec* p, const int* src_ids, int n_src,
+                     const int* out_ids, int n_out,
+                     const uint8_t* coeff /* n_out x n_src */,
+                     const bool* src_null) {
+  const ecx::GF8& f = ecx::gf8();
   for (int i = 0; i < n_src; i++) p->src_ids[i] = src_ids[i];
   for (int j = 0; j < n_out; j++) p->out_ids[j] = out_ids[j];
   for (int j = 0; j < n_out; j++)
@@ -1705,138 +1440,126 @@ static void fill_params(EcLaunchParams* p, const ecx::GF8& f,
     }
 }
 
+static void fill_params(EcLaunchParams* p, const int* src_ids, int n_src,
+                        const int* out_ids, int n_out, const uint8_t* coeff,
+                        const bool* src_null) {
+  p->n_src = n_src;
+  p->n_out = n_out;
+  fill_rec(p, src_ids, n_src, out_ids, n_out, coeff, src_null);
+}
+
+// Knobs are read once per process (A/B-able via env on the GPU box).
+static int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
+// ECX_NT=1 (nontemporal loads/stores) measured +7% encode bandwidth —
+// streaming data with zero reuse should not occupy L1/L2
+// (profiles/rocprof_r01_summary.md).
+static bool env_nt() {
+  static const int v = env_int("ECX_NT", 1);
+  return v != 0;
+}
+
+// One-ahead source prefetch (PF template argument) for an n_out-output
+// launch. ECX_PF: 0 = never, 1 = always, 2/unset = auto (NOUT >= 4, where
+// the all-ones probe measured 15-20% exposed VALU; the NOUT <= 3 shapes are
+// already at their memory floor). 3 selected the removed depth-2 experiment
+// and now means 1.
+static bool matmul_pf(int n_out) {
+  static const int v = env_int("ECX_PF", 2);
+  return v == 1 || v == 3 || (v == 2 && n_out >= 4);
+}
+
 // Grid/variant selection for the matmul kernel, shared by the slot-staged
 // launch_matmul and the pipelined host path (which keeps params resident).
 struct MatmulCfg {
   dim3 grid;
-  int vpt;
   bool nt;
 };
 
 static MatmulCfg matmul_cfg(long vecs, long n_stripes) {
-  // Tunables (A/B-able via env on the GPU box): VPT = 16B vectors per
-  // thread per iteration, TILE = target vectors per thread per launch.
-  // Defaults from the round-1 sweeps (profiles/rocprof_r01_summary.md):
-  // VPT=1 keeps 8 waves/SIMD at NOUT=3 and beat VPT=2; with NT on,
-  // TILE=2 won the grid-shape sweep (6.0 TB/s encode).
-  static const int env_vpt = [] {
-    const char* v = getenv("ECX_VPT");
-    int x = v ? atoi(v) : 1;
-    return (x == 1 || x == 2) ? x : 1;
-  }();
-  static const int env_tile = [] {
-    const char* v = getenv("ECX_TILE");
-    int x = v ? atoi(v) : 2;
-    return x >= 1 ? x : 2;
-  }();
-  // NT=1 (nontemporal loads/stores) measured +7% encode bandwidth —
-  // streaming data with zero reuse should not occupy L1/L2
-  // (profiles/rocprof_r01_summary.md).
-  static const int env_nt = [] {
-    const char* v = getenv("ECX_NT");
-    return v ? atoi(v) : 1;
-  }();
-  MatmulCfg c;
-  c.vpt = (vecs >= 2 * 256) ? env_vpt : 1;
-  const long per_block = 256L * c.vpt;
-  long tiles = (vecs + per_block - 1) / per_block;
-  long loops = std::max(1, env_tile / c.vpt);
+  // ECX_TILE = target vectors per thread per launch. With NT on, TILE=2 won
+  // the round-1 grid-shape sweep (6.0 TB/s encode,
+  // profiles/rocprof_r01_summary.md).
+  static const int env_tile = env_int("ECX_TILE", 2);
+  const long loops = env_tile >= 1 ? env_tile : 2;
+  const long tiles = (vecs + 255) / 256;
   int gx = (int)std::min<long>((tiles + loops - 1) / loops, 1024);
   if (gx < 1) gx = 1;
   // if few stripes, widen x so total blocks cover 256 CUs * a few waves
   while ((long)gx * n_stripes < 2048 && gx < tiles) gx *= 2;
+  MatmulCfg c;
   c.grid = dim3(gx, (unsigned)n_stripes);
-  c.nt = env_nt != 0;
+  c.nt = env_nt();
   return c;
 }
 
-// Template dispatch for one output group (n_out <= 4) with params already
-// resident on the device.
+// Runtime n_out (1-4) and flags to template arguments: fn is called with
+// std::integral_constant<int, n_out> and one std::bool_constant per flag.
+// Returns false (fn not called) when n_out is out of range.
+template <class F>
+static void dispatch_flags(F&& fn) {
+  fn();
+}
+template <class F, class... Rest>
+static void dispatch_flags(F&& fn, bool b, Rest... rest) {
+  if (b)
+    dispatch_flags([&](auto... c) { fn(std::true_type{}, c...); }, rest...);
+  else
+    dispatch_flags([&](auto... c) { fn(std::false_type{}, c...); }, rest...);
+}
+template <class F, class... Flags>
+static bool dispatch_nout(int n_out, F&& fn, Flags... flags) {
+#define ECX_NOUT_CASE(N)                                                  \
+  case N:                                                                 \
+    dispatch_flags(                                                       \
+        [&](auto... c) { fn(std::integral_constant<int, N>{}, c...); },   \
+        flags...);                                                        \
+    return true;
+  switch (n_out) {
+    ECX_NOUT_CASE(1)
+    ECX_NOUT_CASE(2)
+    ECX_NOUT_CASE(3)
+    ECX_NOUT_CASE(4)
+  }
+#undef ECX_NOUT_CASE
+  return false;
+}
+
+// Launch for one output group (n_out <= 4) with params already resident on
+// the device.
 static int matmul_dispatch(hipStream_t stream, const uint8_t* d_buf,
                            uint8_t* d_obuf, const EcLaunchParams* d_params,
-                           int n_out, int n_src, bool accum,
-                           const MatmulCfg& c, size_t chunk_bytes, int cps) {
-  const long vecs = (long)(chunk_bytes >> 4);
-  const dim3 grid = c.grid;
-  const int vpt = c.vpt;
-  const bool env_nt = c.nt;
-  // K8 full source-unroll measured 2.1x SLOWER (16.7 vs 8.0 ms encode:
-  // the unrolled body bloats registers/issue and the dynamic loop already
-  // gets enough MLP from 8 waves/SIMD) — keep available for experiments,
-  // default OFF.
-  static const int env_k8 = [] {
-    const char* v = getenv("ECX_K8");
-    return v ? atoi(v) : 0;
-  }();
-  // one-ahead source prefetch (PF template): keeps a load in flight
-  // across each compute body. ECX_PF: 0 = never, 1 = always, 2/unset =
-  // auto (NOUT >= 4, where the all-ones probe measured 15-20% exposed
-  // VALU; the NOUT <= 3 shapes are already at their memory floor).
-  static const int env_pf = [] {
-    const char* v = getenv("ECX_PF");
-    return v ? atoi(v) : 2;
-  }();
-  // depth: ECX_PF 0 = off, 1 = always depth-1, 2/unset = auto (depth 1
-  // at NOUT >= 4), 3 = always depth-2 (experiment)
-  const int pf = env_pf == 1 ? 1
-                 : env_pf == 3 ? 2
-                 : (env_pf == 2 && n_out >= 4) ? 1 : 0;
-  const bool k8 = env_k8 && !accum && vpt == 1 && n_src == 8;
-#define ECX_LAUNCH(NO, AC, VP, NTF)                                          \
-  do {                                                                       \
-    if (pf == 2)                                                             \
-      hipLaunchKernelGGL((ec_gf_matmul_kernel<NO, AC, VP, NTF, 0, 2>),       \
-                         grid, dim3(256), 0, stream, d_buf, d_obuf,          \
-                         d_params, (long)chunk_bytes, cps, vecs);            \
-    else if (pf == 1)                                                        \
-      hipLaunchKernelGGL((ec_gf_matmul_kernel<NO, AC, VP, NTF, 0, 1>),       \
-                         grid, dim3(256), 0, stream, d_buf, d_obuf,          \
-                         d_params, (long)chunk_bytes, cps, vecs);            \
-    else                                                                     \
-      hipLaunchKernelGGL((ec_gf_matmul_kernel<NO, AC, VP, NTF>), grid,       \
-                         dim3(256), 0, stream, d_buf, d_obuf, d_params,      \
-                         (long)chunk_bytes, cps, vecs);                      \
-  } while (0)
-#define ECX_LAUNCH_K8(NO, NTF)                                               \
-  hipLaunchKernelGGL((ec_gf_matmul_kernel<NO, false, 1, NTF, 8>), grid,      \
-                     dim3(256), 0, stream, d_buf, d_obuf, d_params,          \
-                     (long)chunk_bytes, cps, vecs)
-#define ECX_VARIANT(NO, AC)                          \
-  do {                                               \
-    if (k8) {                                        \
-      if (env_nt) ECX_LAUNCH_K8(NO, true);           \
-      else ECX_LAUNCH_K8(NO, false);                 \
-    } else if (vpt == 2) {                           \
-      if (env_nt) ECX_LAUNCH(NO, AC, 2, true);       \
-      else ECX_LAUNCH(NO, AC, 2, false);             \
-    } else {                                         \
-      if (env_nt) ECX_LAUNCH(NO, AC, 1, true);       \
-      else ECX_LAUNCH(NO, AC, 1, false);             \
-    }                                                \
-  } while (0)
-#define ECX_DISPATCH(NO)              \
-  case NO:                            \
-    if (accum) ECX_VARIANT(NO, true); \
-    else ECX_VARIANT(NO, false);      \
-    break;
-  switch (n_out) {
-    ECX_DISPATCH(1)
-    ECX_DISPATCH(2)
-    ECX_DISPATCH(3)
-    ECX_DISPATCH(4)
-    default:
-      return ECX_ERR_INVAL;
-  }
-#undef ECX_DISPATCH
-#undef ECX_VARIANT
-#undef ECX_LAUNCH_K8
-#undef ECX_LAUNCH
+                           int n_out, bool accum, const MatmulCfg& c,
+                           size_t chunk_bytes, int cps) {
+  const bool ok = dispatch_nout(
+      n_out,
+      [&](auto NO, auto AC, auto NTF, auto PFD) {
+        hipLaunchKernelGGL((ec_gf_matmul_kernel<NO(), AC(), NTF(), PFD()>),
+                           c.grid, dim3(256), 0, stream, d_buf, d_obuf,
+                           d_params, (long)chunk_bytes, cps,
+                           (long)(chunk_bytes >> 4));
+      },
+      accum, c.nt, matmul_pf(n_out));
+  if (!ok) return ECX_ERR_INVAL;
   HIP_TRY(hipGetLastError());
   return ECX_OK;
 }
 
-// Launch the matmul kernel for one output group (n_out <= ECX_MAX_OUT but
-// template-dispatched in groups of <= 4 for register economy).
+// Upload one launch record to the slot's device copy (a ring of one: waits
+// for the previous upload before the pinned copy is rewritten).
+static int upload_params(Slot& s, const EcLaunchParams& params) {
+  HIP_TRY(wait_event(s.ev_param));
+  std::memcpy(s.h_params, &params, sizeof(EcLaunchParams));
+  HIP_TRY(hipMemcpyAsync(s.d_params, s.h_params, sizeof(EcLaunchParams),
+                         hipMemcpyHostToDevice, s.stream));
+  HIP_TRY(hipEventRecord(s.ev_param, s.stream));
+  return ECX_OK;
+}
+
+// Launch the matmul kernel for one output group (n_out <= 4).
 static int launch_matmul(ecx_ctx* ctx, Slot& s, const uint8_t* d_buf,
                          uint8_t* d_obuf, const EcLaunchParams& params,
                          long n_stripes, size_t chunk_bytes, bool accum,
@@ -1844,19 +1567,13 @@ static int launch_matmul(ecx_ctx* ctx, Slot& s, const uint8_t* d_buf,
   if (chunk_bytes % 16 || n_stripes <= 0 || n_stripes > 65535)
     return ECX_ERR_INVAL;
   HIP_TRY(hipSetDevice(ctx->device));
-
-  // wait for any in-flight param upload on this slot, then stage params
-  HIP_TRY(wait_event(s.ev_param));
-  std::memcpy(s.h_params, &params, sizeof(EcLaunchParams));
-  HIP_TRY(hipMemcpyAsync(s.d_params, s.h_params, sizeof(EcLaunchParams),
-                         hipMemcpyHostToDevice, s.stream));
-  HIP_TRY(hipEventRecord(s.ev_param, s.stream));
+  int r = upload_params(s, params);
+  if (r != ECX_OK) return r;
 
   const MatmulCfg c = matmul_cfg((long)(chunk_bytes >> 4), n_stripes);
   if (time_it) HIP_TRY(hipEventRecord(s.ev_start, s.stream));
-  int r = matmul_dispatch(s.stream, d_buf, d_obuf, s.d_params, params.n_out,
-                          params.n_src, accum, c, chunk_bytes,
-                          ctx->k + ctx->m);
+  r = matmul_dispatch(s.stream, d_buf, d_obuf, s.d_params, params.n_out,
+                      accum, c, chunk_bytes, ctx->k + ctx->m);
   if (r != ECX_OK) return r;
   if (time_it) {
     HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
@@ -1870,10 +1587,7 @@ static int launch_matmul(ecx_ctx* ctx, Slot& s, const uint8_t* d_buf,
 // ECX_STREAM: unset/1 = ec_gf_stream_kernel for the non-accumulating batch
 // matmul, 0 = ec_gf_matmul_kernel as before (A/B within one process lease).
 static int env_stream() {
-  static const int v = [] {
-    const char* e = getenv("ECX_STREAM");
-    return e ? atoi(e) : 1;
-  }();
+  static const int v = env_int("ECX_STREAM", 1);
   return v;
 }
 
@@ -1886,21 +1600,15 @@ static int env_stream() {
 // (profiles/stream_kernel_summary.md), grids of many short blocks beat
 // every persistent grid by 4-5% on both legs.
 static int env_stream_bpc() {
-  static const int v = [] {
-    const char* e = getenv("ECX_STREAM_BPC");
-    const int x = e ? atoi(e) : -1;
-    return std::max(-1, std::min(x, 65536));
-  }();
+  static const int v =
+      std::max(-1, std::min(env_int("ECX_STREAM_BPC", -1), 65536));
   return v;
 }
 
 // ECX_STREAM_ORDER: tile walk, 0/unset = tile-in-chunk fastest (concurrent
 // blocks cover a few whole stripes), 1 = stripe fastest.
 static int env_stream_order() {
-  static const int v = [] {
-    const char* e = getenv("ECX_STREAM_ORDER");
-    return e ? atoi(e) : 0;
-  }();
+  static const int v = env_int("ECX_STREAM_ORDER", 0);
   return v;
 }
 
@@ -1995,19 +1703,11 @@ static int launch_stream(ecx_ctx* ctx, Slot& s, const uint8_t* d_buf,
   const uint64_t stripe_bytes = (uint64_t)(ctx->k + ctx->m) * chunk_bytes;
 
   if (time_it) HIP_TRY(hipEventRecord(s.ev_start, s.stream));
-#define ECX_STREAM_LAUNCH(NO)                                               \
-  case NO:                                                                  \
-    hipLaunchKernelGGL((ec_gf_stream_kernel<NO>), dim3(grid), dim3(256), 0, \
-                       s.stream, d_buf, d_obuf, p, stripe_bytes, vecs,      \
-                       n_outer, n_inner, step_q, step_r, order);            \
-    break;
-  switch (n_out) {
-    ECX_STREAM_LAUNCH(1)
-    ECX_STREAM_LAUNCH(2)
-    ECX_STREAM_LAUNCH(3)
-    ECX_STREAM_LAUNCH(4)
-  }
-#undef ECX_STREAM_LAUNCH
+  dispatch_nout(n_out, [&](auto NO) {
+    hipLaunchKernelGGL((ec_gf_stream_kernel<NO()>), dim3(grid), dim3(256), 0,
+                       s.stream, d_buf, d_obuf, p, stripe_bytes, vecs,
+                       n_outer, n_inner, step_q, step_r, order);
+  });
   HIP_TRY(hipGetLastError());
   if (time_it) {
     HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
@@ -2027,7 +1727,6 @@ static int run_matmul(ecx_ctx* ctx, int slot_i, const uint8_t* d_buf,
     return ECX_ERR_INVAL;
   Slot& s = ctx->slots[slot_i];
   std::lock_guard<std::recursive_mutex> g(s.mu);
-  const ecx::GF8& f = ecx::gf8();
   // non-accumulating jobs go to the streaming kernel (its tile
   // counters are 32-bit; no real chunk comes near 2^31 tiles)
   const bool stream = !accum && env_stream() != 0 &&
@@ -2043,11 +1742,8 @@ static int run_matmul(ecx_ctx* ctx, int slot_i, const uint8_t* d_buf,
       continue;
     }
     EcLaunchParams p;
-    std::vector<uint8_t> sub((size_t)nj * n_src);
-    for (int j = 0; j < nj; j++)
-      std::memcpy(&sub[(size_t)j * n_src], &coeff[(size_t)(j0 + j) * n_src],
-                  n_src);
-    fill_params(&p, f, src_ids, n_src, out_ids + j0, nj, sub.data(), src_null);
+    fill_params(&p, src_ids, n_src, out_ids + j0, nj,
+                coeff + (size_t)j0 * n_src, src_null);
     // time only the first group (the dominant kernel for bench)
     int r = launch_matmul(ctx, s, d_buf, d_obuf, p, n_stripes, chunk_bytes,
                           accum, j0 == 0);
@@ -2072,7 +1768,78 @@ static int ensure_jobs(ecx_ctx* ctx, Slot& s, size_t bytes) {
   return ECX_OK;
 }
 
-// Launch the variable-size slice kernel for one <=4-output group.
+static const int SLICE_VPB = 256 * 4;  // vectors per block, slice kernels
+
+static long slice_blocks(size_t bytes) {
+  return (long)((bytes >> 4) + SLICE_VPB - 1) / SLICE_VPB;
+}
+
+// Device addresses of a slice job table, and its extent in s.h_jobs.
+struct SliceJobs {
+  const uint64_t* ptrs;    // [n_slices * cps]
+  const long* slice_vecs;  // [n_slices]
+  const long* block_voff;  // [n_blocks]
+  const int* block_slice;  // [n_blocks]
+  const int* block_rec;    // [n_blocks], only when recs are given
+  long n_blocks;
+  size_t bytes;
+};
+
+// Build the slice kernels' job table in s.h_jobs behind `head` bytes the
+// caller keeps for launch records: [ptrs u64][slice_vecs i64][block_voff
+// i64][block_slice i32][block_rec i32]. Blocks are assigned to the slices
+// order[0..n_order) in that order (order == NULL: every slice once);
+// recs[i], when given, is the record index of the blocks of order[i]. The
+// caller uploads s.h_jobs[0, bytes).
+static int build_slice_jobs(ecx_ctx* ctx, Slot& s, size_t head,
+                            void* const* d_chunks, const size_t* bytes,
+                            int n_slices, const int* order, const int* recs,
+                            size_t n_order, SliceJobs* out) {
+  const int cps = ctx->k + ctx->m;
+  long n_blocks = 0;
+  for (size_t i = 0; i < n_order; i++)
+    n_blocks += slice_blocks(bytes[order ? order[i] : (int)i]);
+  if (n_blocks > (1 << 30)) return ECX_ERR_INVAL;
+  const size_t off_vecs = head + (size_t)n_slices * cps * 8;
+  const size_t off_voff = off_vecs + (size_t)n_slices * 8;
+  const size_t off_bsl = off_voff + (size_t)n_blocks * 8;
+  const size_t off_brec = off_bsl + (size_t)n_blocks * 4;
+  const size_t blob = off_brec + (recs ? (size_t)n_blocks * 4 : 0);
+  int r = ensure_jobs(ctx, s, blob);
+  if (r != ECX_OK) return r;
+  HIP_TRY(wait_event(s.ev_jobs));
+
+  uint64_t* ptrs = (uint64_t*)(s.h_jobs + head);
+  long* svecs = (long*)(s.h_jobs + off_vecs);
+  long* bvoff = (long*)(s.h_jobs + off_voff);
+  int* bslice = (int*)(s.h_jobs + off_bsl);
+  int* brec = (int*)(s.h_jobs + off_brec);
+  for (int i = 0; i < n_slices; i++) {
+    for (int c = 0; c < cps; c++)
+      ptrs[(size_t)i * cps + c] = (uint64_t)d_chunks[(size_t)i * cps + c];
+    svecs[i] = (long)(bytes[i] >> 4);
+  }
+  long b = 0;
+  for (size_t i = 0; i < n_order; i++) {
+    const int sl = order ? order[i] : (int)i;
+    for (long v = 0; v < svecs[sl]; v += SLICE_VPB) {
+      bslice[b] = sl;
+      bvoff[b] = v;
+      if (recs) brec[b] = recs[i];
+      b++;
+    }
+  }
+  *out = {(const uint64_t*)(s.d_jobs + head),
+          (const long*)(s.d_jobs + off_vecs),
+          (const long*)(s.d_jobs + off_voff),
+          (const int*)(s.d_jobs + off_bsl),
+          (const int*)(s.d_jobs + off_brec),
+          n_blocks,
+          blob};
+  return ECX_OK;
+}
+
+// Launch the variable-size slice kernel in groups of <= 4 outputs.
 static int run_slices(ecx_ctx* ctx, int slot_i, void* const* d_chunks,
                       const size_t* bytes, int n_slices, const int* src_ids,
                       int n_src, const int* out_ids, int n_out,
@@ -2087,86 +1854,31 @@ static int run_slices(ecx_ctx* ctx, int slot_i, void* const* d_chunks,
   std::lock_guard<std::recursive_mutex> g(s.mu);
   HIP_TRY(hipSetDevice(ctx->device));
 
-  static const int env_nt = [] {
-    const char* v = getenv("ECX_NT");
-    return v ? atoi(v) : 1;
-  }();
-  const int VECS_PER_BLOCK = 256 * 4;
-
-  // block assignment + blob layout: [ptrs u64][slice_vecs i64]
-  // [block_voff i64][block_slice i32]
-  long n_blocks = 0;
-  for (int i = 0; i < n_slices; i++)
-    n_blocks += (long)((bytes[i] >> 4) + VECS_PER_BLOCK - 1) / VECS_PER_BLOCK;
-  if (n_blocks > (1 << 30)) return ECX_ERR_INVAL;
-  size_t off_ptrs = 0;
-  size_t off_vecs = off_ptrs + (size_t)n_slices * cps * 8;
-  size_t off_voff = off_vecs + (size_t)n_slices * 8;
-  size_t off_bsl = off_voff + (size_t)n_blocks * 8;
-  size_t blob = off_bsl + (size_t)n_blocks * 4;
-  int r = ensure_jobs(ctx, s, blob);
+  SliceJobs jt;
+  int r = build_slice_jobs(ctx, s, 0, d_chunks, bytes, n_slices, nullptr,
+                           nullptr, (size_t)n_slices, &jt);
   if (r != ECX_OK) return r;
-  HIP_TRY(wait_event(s.ev_jobs));
-
-  uint64_t* ptrs = (uint64_t*)(s.h_jobs + off_ptrs);
-  long* svecs = (long*)(s.h_jobs + off_vecs);
-  long* bvoff = (long*)(s.h_jobs + off_voff);
-  int* bslice = (int*)(s.h_jobs + off_bsl);
-  long b = 0;
-  for (int i = 0; i < n_slices; i++) {
-    for (int c = 0; c < cps; c++)
-      ptrs[(size_t)i * cps + c] = (uint64_t)d_chunks[(size_t)i * cps + c];
-    long nv = (long)(bytes[i] >> 4);
-    svecs[i] = nv;
-    for (long v = 0; v < nv; v += VECS_PER_BLOCK) {
-      bslice[b] = i;
-      bvoff[b] = v;
-      b++;
-    }
-  }
-  HIP_TRY(hipMemcpyAsync(s.d_jobs, s.h_jobs, blob, hipMemcpyHostToDevice,
+  HIP_TRY(hipMemcpyAsync(s.d_jobs, s.h_jobs, jt.bytes, hipMemcpyHostToDevice,
                          s.stream));
   HIP_TRY(hipEventRecord(s.ev_jobs, s.stream));
 
-  const uint64_t* d_ptrs = (const uint64_t*)(s.d_jobs + off_ptrs);
-  const long* d_svecs = (const long*)(s.d_jobs + off_vecs);
-  const long* d_bvoff = (const long*)(s.d_jobs + off_voff);
-  const int* d_bslice = (const int*)(s.d_jobs + off_bsl);
-
-  const ecx::GF8& f = ecx::gf8();
   for (int j0 = 0; j0 < n_out; j0 += 4) {
     int nj = std::min(4, n_out - j0);
     EcLaunchParams p;
-    std::vector<uint8_t> sub((size_t)nj * n_src);
-    for (int j = 0; j < nj; j++)
-      std::memcpy(&sub[(size_t)j * n_src], &coeff[(size_t)(j0 + j) * n_src],
-                  n_src);
     // per-slice NULL chunks are handled inside the kernel, not via cls
-    fill_params(&p, f, src_ids, n_src, out_ids + j0, nj, sub.data(), nullptr);
-    HIP_TRY(wait_event(s.ev_param));
-    std::memcpy(s.h_params, &p, sizeof(EcLaunchParams));
-    HIP_TRY(hipMemcpyAsync(s.d_params, s.h_params, sizeof(EcLaunchParams),
-                           hipMemcpyHostToDevice, s.stream));
-    HIP_TRY(hipEventRecord(s.ev_param, s.stream));
-#define ECX_SLAUNCH(NO, NTF)                                                \
-  hipLaunchKernelGGL((ec_gf_slices_kernel<NO, NTF>), dim3((unsigned)n_blocks), \
-                     dim3(256), 0, s.stream, d_ptrs, d_bslice, d_bvoff,     \
-                     d_svecs, s.d_params, cps, VECS_PER_BLOCK)
-#define ECX_SDISPATCH(NO)                  \
-  case NO:                                 \
-    if (env_nt) ECX_SLAUNCH(NO, true);     \
-    else ECX_SLAUNCH(NO, false);           \
-    break;
-    switch (nj) {
-      ECX_SDISPATCH(1)
-      ECX_SDISPATCH(2)
-      ECX_SDISPATCH(3)
-      ECX_SDISPATCH(4)
-      default:
-        return ECX_ERR_INVAL;
-    }
-#undef ECX_SDISPATCH
-#undef ECX_SLAUNCH
+    fill_params(&p, src_ids, n_src, out_ids + j0, nj,
+                coeff + (size_t)j0 * n_src, nullptr);
+    r = upload_params(s, p);
+    if (r != ECX_OK) return r;
+    dispatch_nout(
+        nj,
+        [&](auto NO, auto NTF) {
+          hipLaunchKernelGGL((ec_gf_slices_kernel<NO(), NTF()>),
+                             dim3((unsigned)jt.n_blocks), dim3(256), 0,
+                             s.stream, jt.ptrs, jt.block_slice, jt.block_voff,
+                             jt.slice_vecs, s.d_params, cps, SLICE_VPB);
+        },
+        env_nt());
     HIP_TRY(hipGetLastError());
   }
   return ECX_OK;
@@ -2189,11 +1901,6 @@ static int run_bitmatrix(ecx_ctx* ctx, int slot_i, const uint8_t* d_buf,
   Slot& s = ctx->slots[slot_i];
   std::lock_guard<std::recursive_mutex> g(s.mu);
   HIP_TRY(hipSetDevice(ctx->device));
-
-  static const int env_nt = [] {
-    const char* v = getenv("ECX_NT");
-    return v ? atoi(v) : 1;
-  }();
 
   // LDS window: largest power-of-two divisor of pkt within the LDS budget
   // (ECX_BITQ KB). Default 16 from the MI355X sweep: small windows keep
@@ -2254,7 +1961,7 @@ static int run_bitmatrix(ecx_ctx* ctx, int slot_i, const uint8_t* d_buf,
     if (time_it) HIP_TRY(hipEventRecord(s.ev_start, s.stream));
 #define ECX_BRK(NR_)                                                    \
   hipLaunchKernelGGL(                                                   \
-      (env_nt ? (accum ? ec_bitmatrix_reg_kernel<true, true, NR_>       \
+      (env_nt() ? (accum ? ec_bitmatrix_reg_kernel<true, true, NR_>       \
                        : ec_bitmatrix_reg_kernel<true, false, NR_>)     \
               : (accum ? ec_bitmatrix_reg_kernel<false, true, NR_>      \
                        : ec_bitmatrix_reg_kernel<false, false, NR_>)),  \
@@ -2367,7 +2074,7 @@ static int run_bitmatrix(ecx_ctx* ctx, int slot_i, const uint8_t* d_buf,
   size_t lds = (pipe ? 2 * data_bytes : data_bytes) + ops_bytes;
   if (time_it) HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   if (pipe) {
-    auto kfn = env_nt ? (accum ? ec_bitmatrix_pipe_kernel<true, true>
+    auto kfn = env_nt() ? (accum ? ec_bitmatrix_pipe_kernel<true, true>
                                : ec_bitmatrix_pipe_kernel<true, false>)
                       : (accum ? ec_bitmatrix_pipe_kernel<false, true>
                                : ec_bitmatrix_pipe_kernel<false, false>);
@@ -2380,7 +2087,7 @@ static int run_bitmatrix(ecx_ctx* ctx, int slot_i, const uint8_t* d_buf,
         env_xcd && windows_per_sw == 8 && n_windows % ((long)wpb * 64) == 0 &&
         n_blocks % 64 == 0;
 #define ECX_BMK(VQS_)                                                \
-  (env_nt ? (accum ? ec_bitmatrix_kernel<true, true, VQS_>           \
+  (env_nt() ? (accum ? ec_bitmatrix_kernel<true, true, VQS_>           \
                    : ec_bitmatrix_kernel<true, false, VQS_>)         \
           : (accum ? ec_bitmatrix_kernel<false, true, VQS_>          \
                    : ec_bitmatrix_kernel<false, false, VQS_>))
@@ -2447,10 +2154,6 @@ static int run_matmul16(ecx_ctx* ctx, int slot_i, const uint8_t* d_buf,
   Slot& s = ctx->slots[slot_i];
   std::lock_guard<std::recursive_mutex> g(s.mu);
   HIP_TRY(hipSetDevice(ctx->device));
-  static const int env_nt = [] {
-    const char* v = getenv("ECX_NT");
-    return v ? atoi(v) : 1;
-  }();
   const ecx::GF16& f = ecx::gf16();
   const long vecs = (long)(chunk_bytes >> 4);
   int gx = (int)std::min<long>((vecs + 256 * 2 - 1) / (256 * 2), 1024);
@@ -2484,30 +2187,14 @@ static int run_matmul16(ecx_ctx* ctx, int slot_i, const uint8_t* d_buf,
                            s.stream));
     HIP_TRY(hipEventRecord(s.ev_jobs, s.stream));
     if (j0 == 0 && time_all) HIP_TRY(hipEventRecord(s.ev_start, s.stream));
-#define ECX_L16(NO, AC, NTF)                                                \
-  hipLaunchKernelGGL((ec_gf16_matmul_kernel<NO, AC, NTF>), grid, dim3(256), \
-                     0, s.stream, d_buf, d_obuf, s.d_jobs,                  \
-                     (long)chunk_bytes, cps, vecs)
-#define ECX_D16(NO)                                \
-  case NO:                                         \
-    if (accum) {                                   \
-      if (env_nt) ECX_L16(NO, true, true);         \
-      else ECX_L16(NO, true, false);               \
-    } else {                                       \
-      if (env_nt) ECX_L16(NO, false, true);        \
-      else ECX_L16(NO, false, false);              \
-    }                                              \
-    break;
-    switch (nj) {
-      ECX_D16(1)
-      ECX_D16(2)
-      ECX_D16(3)
-      ECX_D16(4)
-      default:
-        return ECX_ERR_INVAL;
-    }
-#undef ECX_D16
-#undef ECX_L16
+    dispatch_nout(
+        nj,
+        [&](auto NO, auto AC, auto NTF) {
+          hipLaunchKernelGGL((ec_gf16_matmul_kernel<NO(), AC(), NTF()>), grid,
+                             dim3(256), 0, s.stream, d_buf, d_obuf, s.d_jobs,
+                             (long)chunk_bytes, cps, vecs);
+        },
+        accum, env_nt());
     HIP_TRY(hipGetLastError());
     if (time_all) {
       HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
@@ -2517,40 +2204,41 @@ static int run_matmul16(ecx_ctx* ctx, int slot_i, const uint8_t* d_buf,
   return ECX_OK;
 }
 
-static int get_plan16(ecx_ctx* ctx, uint64_t present_mask,
-                      Decode16Plan& out) {
+// Decode plan for a mask from `cache` (w=16 and bitmatrix plans: cleared
+// when full), composed by compose(plan) on a miss.
+template <class Plan, class Compose>
+static int get_cached_plan(ecx_ctx* ctx, std::map<uint64_t, Plan>& cache,
+                           uint64_t present_mask, Plan& out,
+                           Compose&& compose) {
   std::lock_guard<std::mutex> g(ctx->lru_mu);
-  auto it = ctx->lru16.find(present_mask);
-  if (it != ctx->lru16.end()) {
+  auto it = cache.find(present_mask);
+  if (it != cache.end()) {
     out = it->second;
     return ECX_OK;
   }
-  Decode16Plan plan;
-  if (!ecx::compose_decode_rows16(ctx->gen16, ctx->k, ctx->m, present_mask,
-                                  plan.survivors, plan.erased, plan.rows))
-    return ECX_ERR_IO;
-  if (ctx->lru16.size() > ecx_ctx::LRU_DEPTH) ctx->lru16.clear();
-  ctx->lru16.emplace(present_mask, plan);
+  Plan plan;
+  if (!compose(plan)) return ECX_ERR_IO;
+  if (cache.size() > ecx_ctx::LRU_DEPTH) cache.clear();
+  cache.emplace(present_mask, plan);
   out = plan;
   return ECX_OK;
 }
 
+static int get_plan16(ecx_ctx* ctx, uint64_t present_mask,
+                      Decode16Plan& out) {
+  return get_cached_plan(ctx, ctx->lru16, present_mask, out, [&](auto& p) {
+    return ecx::compose_decode_rows16(ctx->gen16, ctx->k, ctx->m,
+                                      present_mask, p.survivors, p.erased,
+                                      p.rows);
+  });
+}
+
 static int get_bit_plan(ecx_ctx* ctx, uint64_t present_mask, BitPlan& out) {
-  std::lock_guard<std::mutex> g(ctx->lru_mu);
-  auto it = ctx->bit_lru.find(present_mask);
-  if (it != ctx->bit_lru.end()) {
-    out = it->second;
-    return ECX_OK;
-  }
-  BitPlan plan;
-  if (!ecx::compose_bit_decode_rows(ctx->bitmat, ctx->k, ctx->m, ctx->w,
-                                    present_mask, plan.survivors,
-                                    plan.erased, plan.rows))
-    return ECX_ERR_IO;
-  if (ctx->bit_lru.size() > ecx_ctx::LRU_DEPTH) ctx->bit_lru.clear();
-  ctx->bit_lru.emplace(present_mask, plan);
-  out = plan;
-  return ECX_OK;
+  return get_cached_plan(ctx, ctx->bit_lru, present_mask, out, [&](auto& p) {
+    return ecx::compose_bit_decode_rows(ctx->bitmat, ctx->k, ctx->m, ctx->w,
+                                        present_mask, p.survivors, p.erased,
+                                        p.rows);
+  });
 }
 
 static int get_decode_plan(ecx_ctx* ctx, uint64_t present_mask,
@@ -2601,72 +2289,18 @@ static int multi_resolve(ecx_ctx* ctx, const uint64_t* masks, long n,
   return ECX_OK;
 }
 
-// Launch records [plan * n_pass + pass] from fill_params' output; passes a
-// plan does not have stay zeroed and are never referenced.
+// Launch records [plan * n_pass + pass]; passes a plan does not have stay
+// zeroed and are never referenced.
 static void multi_fill_recs(EcMultiRec* recs, const ecx::MultiGrouping& g,
                             const std::vector<DecodePlan>& plans, int k) {
-  const ecx::GF8& f = ecx::gf8();
   std::memset(recs, 0, sizeof(EcMultiRec) * plans.size() * g.n_pass);
   for (size_t pl = 0; pl < plans.size(); pl++) {
     const DecodePlan& dp = plans[pl];
     const int e = (int)dp.erased.size();
-    for (int pass = 0; pass * ECX_MULTI_OUT < e; pass++) {
-      const int j0 = pass * ECX_MULTI_OUT;
-      const int nj = std::min(ECX_MULTI_OUT, e - j0);
-      EcLaunchParams p;
-      std::memset(&p, 0, sizeof(p));
-      fill_params(&p, f, dp.survivors.data(), k, dp.erased.data() + j0, nj,
-                  dp.rows.data() + (size_t)j0 * k, nullptr);
-      EcMultiRec& r = recs[pl * g.n_pass + pass];
-      std::memcpy(r.src_ids, p.src_ids, sizeof(int) * k);
-      std::memcpy(r.out_ids, p.out_ids, sizeof(int) * nj);
-      std::memcpy(r.cls, p.cls, (size_t)nj * k);
-      std::memcpy(r.tabs, p.tabs, sizeof(uint32_t) * 6 * nj * k);
-    }
-  }
-}
-
-// same policy as matmul_dispatch: one-ahead source prefetch at NOUT >= 4
-static int multi_pf(int n_out) {
-  static const int env_pf = [] {
-    const char* v = getenv("ECX_PF");
-    return v ? atoi(v) : 2;
-  }();
-  return (env_pf == 1 || env_pf == 3) ? 1 : (env_pf == 2 && n_out >= 4) ? 1 : 0;
-}
-
-struct MultiArgs {
-  uint8_t* buf;
-  const EcMultiRec* recs;
-  const int* plan_of_stripe;
-  const int* stripe_list;
-  int n_src, pass, n_pass;
-  long chunk_bytes;
-  int cps;
-  long vecs;
-};
-
-template <int NO, int VP, bool NTF, int PFD>
-static void multi_launch1(dim3 grid, hipStream_t st, const MultiArgs& a) {
-  hipLaunchKernelGGL((ec_gf_matmul_multi_kernel<NO, VP, NTF, PFD>), grid,
-                     dim3(256), 0, st, a.buf, a.buf, a.recs, a.plan_of_stripe,
-                     a.stripe_list, a.n_src, a.pass, a.n_pass, a.chunk_bytes,
-                     a.cps, a.vecs);
-}
-
-template <int NO>
-static void multi_launch(const MatmulCfg& c, int pf, hipStream_t st,
-                         const MultiArgs& a) {
-  if (c.vpt == 2) {
-    if (c.nt) pf ? multi_launch1<NO, 2, true, 1>(c.grid, st, a)
-                 : multi_launch1<NO, 2, true, 0>(c.grid, st, a);
-    else pf ? multi_launch1<NO, 2, false, 1>(c.grid, st, a)
-            : multi_launch1<NO, 2, false, 0>(c.grid, st, a);
-  } else {
-    if (c.nt) pf ? multi_launch1<NO, 1, true, 1>(c.grid, st, a)
-                 : multi_launch1<NO, 1, true, 0>(c.grid, st, a);
-    else pf ? multi_launch1<NO, 1, false, 1>(c.grid, st, a)
-            : multi_launch1<NO, 1, false, 0>(c.grid, st, a);
+    for (int j0 = 0; j0 < e; j0 += ECX_MULTI_OUT)
+      fill_rec(&recs[pl * g.n_pass + j0 / ECX_MULTI_OUT], dp.survivors.data(),
+               k, dp.erased.data() + j0, std::min(ECX_MULTI_OUT, e - j0),
+               dp.rows.data() + (size_t)j0 * k, nullptr);
   }
 }
 
@@ -2858,30 +2492,27 @@ int ecx_decode_batch_multi(ecx_ctx* ctx, void* dptr, long n_stripes,
                          s.stream));
   HIP_TRY(hipEventRecord(s.ev_jobs, s.stream));
 
-  MultiArgs a;
-  a.buf = (uint8_t*)dptr;
-  a.recs = (const EcMultiRec*)s.d_jobs;
-  a.plan_of_stripe = (const int*)(s.d_jobs + off_pos);
-  a.stripe_list = (const int*)(s.d_jobs + off_list);
-  a.n_src = ctx->k;
-  a.n_pass = grp.n_pass;
-  a.chunk_bytes = (long)chunk_bytes;
-  a.cps = ctx->k + ctx->m;
-  a.vecs = (long)(chunk_bytes >> 4);
+  uint8_t* buf = (uint8_t*)dptr;
+  const EcMultiRec* d_recs = (const EcMultiRec*)s.d_jobs;
+  const int* d_pos = (const int*)(s.d_jobs + off_pos);
+  const int* d_list = (const int*)(s.d_jobs + off_list);
+  const long vecs = (long)(chunk_bytes >> 4);
   // one event pair around the whole call, launches back to back
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   for (const auto& l : grp.launches) {
-    const MatmulCfg c = matmul_cfg(a.vecs, (long)l.members.size());
-    const int pf = multi_pf(l.n_out);
-    a.pass = l.pass;
-    switch (l.n_out) {
-      case 1: multi_launch<1>(c, pf, s.stream, a); break;
-      case 2: multi_launch<2>(c, pf, s.stream, a); break;
-      case 3: multi_launch<3>(c, pf, s.stream, a); break;
-      default: multi_launch<4>(c, pf, s.stream, a); break;
-    }
+    const MatmulCfg c = matmul_cfg(vecs, (long)l.members.size());
+    const bool ok = dispatch_nout(
+        l.n_out,
+        [&](auto NO, auto NTF, auto PFD) {
+          hipLaunchKernelGGL(
+              (ec_gf_matmul_multi_kernel<NO(), NTF(), PFD()>), c.grid,
+              dim3(256), 0, s.stream, buf, buf, d_recs, d_pos, d_list, ctx->k,
+              l.pass, grp.n_pass, (long)chunk_bytes, ctx->k + ctx->m, vecs);
+        },
+        c.nt, matmul_pf(l.n_out));
+    if (!ok) return ECX_ERR_INVAL;
     HIP_TRY(hipGetLastError());
-    a.stripe_list += l.members.size();
+    d_list += l.members.size();
   }
   HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
   s.timed = true;
@@ -2916,90 +2547,40 @@ int ecx_decode_slices_multi(ecx_ctx* ctx, void* const* d_chunks,
   }
   if (grp.launches.empty()) return ECX_OK;
 
-  static const int env_nt = [] {
-    const char* v = getenv("ECX_NT");
-    return v ? atoi(v) : 1;
-  }();
-  const int VECS_PER_BLOCK = 256 * 4;
-  auto blocks_of = [&](int sl) {
-    return (long)((bytes[sl] >> 4) + VECS_PER_BLOCK - 1) / VECS_PER_BLOCK;
-  };
-  long n_blocks = 0;
-  for (const auto& l : grp.launches)
-    for (int sl : l.members) n_blocks += blocks_of(sl);
-  if (n_blocks > (1 << 30)) return ECX_ERR_INVAL;
-
-  // blob: [records][ptrs u64][slice_vecs i64][block_voff i64]
-  // [block_slice i32][block_rec i32]; block tables in launch order
-  const size_t n_recs = plans.size() * (size_t)grp.n_pass;
-  const size_t off_ptrs = n_recs * sizeof(EcMultiRec);
-  const size_t off_vecs = off_ptrs + (size_t)n_slices * cps * 8;
-  const size_t off_voff = off_vecs + (size_t)n_slices * 8;
-  const size_t off_bsl = off_voff + (size_t)n_blocks * 8;
-  const size_t off_brec = off_bsl + (size_t)n_blocks * 4;
-  const size_t blob = off_brec + (size_t)n_blocks * 4;
-  r = ensure_jobs(ctx, s, blob);
-  if (r != ECX_OK) return r;
-  HIP_TRY(wait_event(s.ev_jobs));
-
-  multi_fill_recs((EcMultiRec*)s.h_jobs, grp, plans, k);
-  uint64_t* ptrs = (uint64_t*)(s.h_jobs + off_ptrs);
-  long* svecs = (long*)(s.h_jobs + off_vecs);
-  long* bvoff = (long*)(s.h_jobs + off_voff);
-  int* bslice = (int*)(s.h_jobs + off_bsl);
-  int* brec = (int*)(s.h_jobs + off_brec);
-  for (int i = 0; i < n_slices; i++) {
-    for (int c = 0; c < cps; c++)
-      ptrs[(size_t)i * cps + c] = (uint64_t)d_chunks[(size_t)i * cps + c];
-    svecs[i] = (long)(bytes[i] >> 4);
-  }
-  long b = 0;
+  // job table behind the records, block tables in launch order
+  std::vector<int> order, rec_of;
   for (const auto& l : grp.launches)
     for (int sl : l.members) {
-      const int rec = grp.plan_of_stripe[sl] * grp.n_pass + l.pass;
-      for (long v = 0; v < svecs[sl]; v += VECS_PER_BLOCK) {
-        bslice[b] = sl;
-        bvoff[b] = v;
-        brec[b] = rec;
-        b++;
-      }
+      order.push_back(sl);
+      rec_of.push_back(grp.plan_of_stripe[sl] * grp.n_pass + l.pass);
     }
-  HIP_TRY(hipMemcpyAsync(s.d_jobs, s.h_jobs, blob, hipMemcpyHostToDevice,
+  const size_t n_recs = plans.size() * (size_t)grp.n_pass;
+  SliceJobs jt;
+  r = build_slice_jobs(ctx, s, n_recs * sizeof(EcMultiRec), d_chunks, bytes,
+                       n_slices, order.data(), rec_of.data(), order.size(),
+                       &jt);
+  if (r != ECX_OK) return r;
+  multi_fill_recs((EcMultiRec*)s.h_jobs, grp, plans, k);
+  HIP_TRY(hipMemcpyAsync(s.d_jobs, s.h_jobs, jt.bytes, hipMemcpyHostToDevice,
                          s.stream));
   HIP_TRY(hipEventRecord(s.ev_jobs, s.stream));
-
-  const EcMultiRec* d_recs = (const EcMultiRec*)s.d_jobs;
-  const uint64_t* d_ptrs = (const uint64_t*)(s.d_jobs + off_ptrs);
-  const long* d_svecs = (const long*)(s.d_jobs + off_vecs);
-  const long* d_bvoff = (const long*)(s.d_jobs + off_voff);
-  const int* d_bslice = (const int*)(s.d_jobs + off_bsl);
-  const int* d_brec = (const int*)(s.d_jobs + off_brec);
 
   HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   long b0 = 0;
   for (const auto& l : grp.launches) {
     long nb = 0;
-    for (int sl : l.members) nb += blocks_of(sl);
-#define ECX_SMLAUNCH(NO, NTF)                                               \
-  hipLaunchKernelGGL((ec_gf_slices_multi_kernel<NO, NTF>),                  \
-                     dim3((unsigned)nb), dim3(256), 0, s.stream, d_ptrs,    \
-                     d_bslice + b0, d_bvoff + b0, d_brec + b0, d_svecs,     \
-                     d_recs, k, cps, VECS_PER_BLOCK)
-#define ECX_SMDISPATCH(NO)                  \
-  case NO:                                  \
-    if (env_nt) ECX_SMLAUNCH(NO, true);     \
-    else ECX_SMLAUNCH(NO, false);           \
-    break;
-    switch (l.n_out) {
-      ECX_SMDISPATCH(1)
-      ECX_SMDISPATCH(2)
-      ECX_SMDISPATCH(3)
-      ECX_SMDISPATCH(4)
-      default:
-        return ECX_ERR_INVAL;
-    }
-#undef ECX_SMDISPATCH
-#undef ECX_SMLAUNCH
+    for (int sl : l.members) nb += slice_blocks(bytes[sl]);
+    const bool ok = dispatch_nout(
+        l.n_out,
+        [&](auto NO, auto NTF) {
+          hipLaunchKernelGGL((ec_gf_slices_multi_kernel<NO(), NTF()>),
+                             dim3((unsigned)nb), dim3(256), 0, s.stream,
+                             jt.ptrs, jt.block_slice + b0, jt.block_voff + b0,
+                             jt.block_rec + b0, jt.slice_vecs,
+                             (const EcMultiRec*)s.d_jobs, k, cps, SLICE_VPB);
+        },
+        env_nt());
+    if (!ok) return ECX_ERR_INVAL;
     HIP_TRY(hipGetLastError());
     b0 += nb;
   }
@@ -3093,16 +2674,11 @@ int ecx_matmul_chunks_host(ecx_ctx* ctx, const uint8_t* const* srcs,
   int src_ids[ECX_MAX_K], out_ids[ECX_MAX_K];
   for (int i = 0; i < n_src; i++) src_ids[i] = i;
   for (int j = 0; j < n_out; j++) out_ids[j] = n_src + j;
-  const ecx::GF8& f = ecx::gf8();
   for (int j0 = 0; j0 < n_out; j0 += 4) {
     int nj = std::min(4, n_out - j0);
     EcLaunchParams p;
-    std::vector<uint8_t> sub((size_t)nj * n_src);
-    for (int j = 0; j < nj; j++)
-      std::memcpy(&sub[(size_t)j * n_src], &rows[(size_t)(j0 + j) * n_src],
-                  n_src);
-    fill_params(&p, f, src_ids, n_src, out_ids + j0, nj, sub.data(),
-                src_null);
+    fill_params(&p, src_ids, n_src, out_ids + j0, nj,
+                rows + (size_t)j0 * n_src, src_null);
     int rr = launch_matmul(ctx, s, s.d_stage, s.d_stage, p, 1, bytes, false,
                            false);
     if (rr != ECX_OK) return rr;
@@ -3593,7 +3169,6 @@ static int pipelined_matmul_host(ecx_ctx* ctx, Slot& s,
   for (int i = 0; i < n_src; i++) any_null |= src_null[i];
   const int want_kind = (cache_kind != 0 && !any_null) ? cache_kind : 0;
   if (want_kind == 0 || s.pparams_kind != want_kind) {
-    const ecx::GF8& f = ecx::gf8();
     // a previous successful call drained both pipe events, but an errored
     // one may not have: make the pinned param area provably safe to rewrite
     HIP_TRY(wait_event(s.ev_pipe[0]));
@@ -3601,7 +3176,7 @@ static int pipelined_matmul_host(ecx_ctx* ctx, Slot& s,
     s.pparams_kind = 0;
     for (int g = 0; g < groups; g++) {
       const int j0 = 4 * g, nj = std::min(4, n_out - j0);
-      fill_params(&s.h_pparams[g], f, src_ids, n_src, out_ids + j0, nj,
+      fill_params(&s.h_pparams[g], src_ids, n_src, out_ids + j0, nj,
                   rows + (size_t)j0 * n_src, src_null);
     }
     HIP_TRY(hipMemcpyAsync(s.d_pparams, s.h_pparams,
@@ -3657,8 +3232,8 @@ static int pipelined_matmul_host(ecx_ctx* ctx, Slot& s,
       const MatmulCfg c = matmul_cfg((long)(tl >> 4), 1);
       for (int g = 0; g < groups && rc == ECX_OK; g++) {
         const int nj = std::min(4, n_out - 4 * g);
-        rc = matmul_dispatch(s.stream, dbuf, dbuf, s.d_pparams + g, nj,
-                             n_src, false, c, tl, cps);
+        rc = matmul_dispatch(s.stream, dbuf, dbuf, s.d_pparams + g, nj, false,
+                             c, tl, cps);
       }
       if (rc == ECX_OK) {
         he = hipMemcpyAsync(hbuf + (size_t)n_src * tl,
@@ -3725,7 +3300,7 @@ static int pipelined_matmul_host(ecx_ctx* ctx, Slot& s,
     for (int g = 0; g < groups; g++) {
       const int nj = std::min(4, n_out - 4 * g);
       int rr = matmul_dispatch(s.stream, dbuf, dbuf, s.d_pparams + g, nj,
-                               n_src, false, c, tl, cps);
+                               false, c, tl, cps);
       if (rr != ECX_OK) {
         (void)hipStreamSynchronize(s.stream);  // quiesce in-flight tiles
         return rr;
@@ -3831,14 +3406,11 @@ int ecx_encode_chunks_host(ecx_ctx* ctx, const uint8_t* const* data,
     }
   } else {
   const uint8_t* rows = ctx->gen.data() + (size_t)k * k;
-  const ecx::GF8& f = ecx::gf8();
   for (int j0 = 0; j0 < m; j0 += 4) {
     int nj = std::min(4, m - j0);
     EcLaunchParams p;
-    std::vector<uint8_t> sub((size_t)nj * k);
-    for (int j = 0; j < nj; j++)
-      std::memcpy(&sub[(size_t)j * k], &rows[(size_t)(j0 + j) * k], k);
-    fill_params(&p, f, src_ids, k, out_ids + j0, nj, sub.data(), src_null);
+    fill_params(&p, src_ids, k, out_ids + j0, nj, rows + (size_t)j0 * k,
+                src_null);
     int rr = launch_matmul(ctx, s, s.d_stage, s.d_stage, p, 1, chunk_bytes,
                            false, false);
     if (rr != ECX_OK) return rr;
@@ -4009,15 +3581,11 @@ int ecx_decode_chunks_host(ecx_ctx* ctx, uint8_t* const* chunks,
     HIP_TRY(hipMemcpyAsync(s.d_stage + (size_t)id * chunk_bytes, chunks[id],
                            chunk_bytes, hipMemcpyHostToDevice, s.stream));
   }
-  const ecx::GF8& f = ecx::gf8();
   for (size_t j0 = 0; j0 < plan.erased.size(); j0 += 4) {
     int nj = (int)std::min<size_t>(4, plan.erased.size() - j0);
     EcLaunchParams p;
-    std::vector<uint8_t> sub((size_t)nj * k);
-    for (int j = 0; j < nj; j++)
-      std::memcpy(&sub[(size_t)j * k], &plan.rows[(j0 + j) * k], k);
-    fill_params(&p, f, plan.survivors.data(), k, plan.erased.data() + j0, nj,
-                sub.data(), src_null);
+    fill_params(&p, plan.survivors.data(), k, plan.erased.data() + j0, nj,
+                plan.rows.data() + j0 * k, src_null);
     int rr = launch_matmul(ctx, s, s.d_stage, s.d_stage, p, 1, chunk_bytes,
                            false, false);
     if (rr != ECX_OK) return rr;
