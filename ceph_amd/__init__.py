@@ -113,6 +113,10 @@ def _lib():
                                     ctypes.c_int, ctypes.c_void_p]
     lib.ecx_gf8_tabs332_probe.argtypes = [ctypes.c_uint8,
                                           ctypes.POINTER(ctypes.c_uint32)]
+    lib.ecx_stream_walk_probe.argtypes = [
+        ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
+        ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
+        ctypes.POINTER(ctypes.c_uint32), ctypes.c_int]
     lib.ecx_sync.argtypes = [ctypes.c_void_p, ctypes.c_int]
     lib.ecx_last_kernel_ms.argtypes = [ctypes.c_void_p, ctypes.c_int,
                                        ctypes.POINTER(ctypes.c_double)]
@@ -165,6 +169,24 @@ def gf8_tabs332_probe(c):
         c, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))),
         "ecx_gf8_tabs332_probe")
     return out
+
+
+def stream_walk_probe(n_stripes, tiles_per_chunk, width, xcd, grid, hw_block):
+    """CPU-only: the (stripe, tile) pairs, as an (n, 2) uint32 array in visit
+    order, that one hardware block of the streaming batch kernel takes under
+    stripe-group width `width` and the XCD-contiguous mapping `xcd`."""
+    # the walk rounds the stripe count up to whole groups: under 2x the tiles
+    cap = (2 * n_stripes * tiles_per_chunk) // max(1, grid) + 2
+    st = np.zeros(cap, dtype=np.uint32)
+    ti = np.zeros(cap, dtype=np.uint32)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    n = _ck(lib().ecx_stream_walk_probe(
+        n_stripes, tiles_per_chunk, width, int(bool(xcd)), grid, hw_block,
+        st.ctypes.data_as(u32p), ti.ctypes.data_as(u32p), cap),
+        "ecx_stream_walk_probe")
+    if n > cap:
+        raise EcError(f"ecx_stream_walk_probe: block visits {n} > {cap} tiles")
+    return np.stack([st[:n], ti[:n]], axis=1)
 
 
 def _ck(r, what):

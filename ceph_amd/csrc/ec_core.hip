@@ -48,6 +48,7 @@
 #include "../../include/ec_mi355x.h"
 #include "gf.h"
 #include "decode_multi.h"
+#include "stream_walk.h"
 
 // ---------------------------------------------------------------------------
 // Kernel-side
@@ -293,18 +294,16 @@ __device__ __forceinline__ void ecx_stream_source(
 }
 
 // A tile is 256 lanes x 16 B of one chunk position range of one stripe.
-// Tiles are numbered outer * n_inner + inner and block b walks tiles b,
-// b + gridDim.x, ... (the grid may be anything from one block per tile to a
-// persistent one); (step_q, step_r) = divmod(gridDim.x, n_inner) from the
-// host keeps the walk free of per-tile division. stripe_fastest == 0:
-// inner = tile within the chunk, outer = stripe; 1: the other way round.
+// Which tiles a block takes, and in which order, is the walk of
+// stream_walk.h: every value of it is launch-uniform and host-computed, the
+// position lives in SGPRs and a step is three adds with carries. The grid
+// may be anything from one block per tile to a persistent one.
 // Register budget: 8 waves/SIMD (<= 64 VGPRs) for NOUT <= 3; NOUT = 4 needs
 // about 73 and would spill at 64, so it is asked for 6.
 template <int NOUT>
 __global__ __launch_bounds__(256, NOUT < 4 ? 8 : 6) void ec_gf_stream_kernel(
     const uint8_t* buf, uint8_t* obuf, const EcStreamParams p,
-    uint64_t stripe_bytes, uint64_t vecs_per_chunk, uint32_t n_outer,
-    uint32_t n_inner, uint32_t step_q, uint32_t step_r, int stripe_fastest) {
+    uint64_t stripe_bytes, uint64_t vecs_per_chunk, const EcxWalk walk) {
   const uint32_t voff = threadIdx.x << 4;
   const int n_src = p.n_src;
   uint32_t one_mask[NOUT], mul_mask[NOUT];
@@ -313,15 +312,16 @@ __global__ __launch_bounds__(256, NOUT < 4 ? 8 : 6) void ec_gf_stream_kernel(
     one_mask[j] = p.one_mask[j];
     mul_mask[j] = p.mul_mask[j];
   }
-  uint32_t a = blockIdx.x / n_inner;
-  uint32_t b = blockIdx.x - a * n_inner;
-  while (a < n_outer) {
-    const uint32_t stripe = stripe_fastest ? b : a;
-    const uint32_t tile = stripe_fastest ? a : b;
+  EcxWalkPos pos = ecx_walk_start(walk, blockIdx.x);
+  while (ecx_walk_live(walk, pos)) {
+    const uint32_t stripe = ecx_walk_stripe(walk, pos);
+    const uint32_t tile = pos.t;
     // wave-uniform 64-bit base; the per-lane part stays a 32-bit offset
     const uint64_t tbase =
         (uint64_t)stripe * stripe_bytes + ((uint64_t)tile << 12);
-    if (((uint64_t)tile << 8) + threadIdx.x < vecs_per_chunk) {
+    // stripe >= n_stripes: the skipped end of a last, narrower stripe group
+    if (stripe < walk.n_stripes &&
+        ((uint64_t)tile << 8) + threadIdx.x < vecs_per_chunk) {
       const uint8_t* sb = buf + tbase;
       uint32_t acc[NOUT][4];
 #pragma unroll
@@ -371,12 +371,7 @@ __global__ __launch_bounds__(256, NOUT < 4 ? 8 : 6) void ec_gf_stream_kernel(
             o, reinterpret_cast<v4u*>(ob + p.out_off[j] + voff));
       }
     }
-    a += step_q;
-    b += step_r;
-    if (b >= n_inner) {
-      b -= n_inner;
-      a++;
-    }
+    ecx_walk_next(walk, pos);
   }
 }
 
@@ -1591,14 +1586,15 @@ static int env_stream() {
   return v;
 }
 
-// ECX_STREAM_BPC: grid size. Unset = the measured default: two tiles per
-// block, but no fewer blocks than fill the GPU (8 per CU) while tiles last
-// - at the flagship shape 524,288 blocks of two tiles. N >= 1 = N blocks
-// per CU (grid = min(tiles, CUs x N), each block grid-strides over its
-// tiles); 0 = the persistent grid, as many blocks per CU as the occupancy
-// query says stay resident. Measured at the flagship shape
-// (profiles/stream_kernel_summary.md), grids of many short blocks beat
-// every persistent grid by 4-5% on both legs.
+// ECX_STREAM_BPC: grid size. Unset = the measured default: one block per
+// tile (1,048,576 blocks at the flagship shape; beyond 2^23 tiles the blocks
+// grid-stride). N >= 1 = N blocks per CU (grid = min(tiles, CUs x N), each
+// block grid-strides over its tiles); 0 = the persistent grid, as many
+// blocks per CU as the occupancy query says stay resident. Measured at the
+// flagship shape, grids of many short blocks beat every persistent grid by
+// 4-5% on both legs (profiles/stream_kernel_summary.md), and under the
+// XCD-contiguous mapping one tile per block beats two
+// (profiles/stream_walk_summary.md).
 static int env_stream_bpc() {
   static const int v =
       std::max(-1, std::min(env_int("ECX_STREAM_BPC", -1), 65536));
@@ -1606,9 +1602,29 @@ static int env_stream_bpc() {
 }
 
 // ECX_STREAM_ORDER: tile walk, 0/unset = tile-in-chunk fastest (concurrent
-// blocks cover a few whole stripes), 1 = stripe fastest.
+// blocks cover a few whole stripes), 1 = stripe fastest. These are the two
+// ends of ECX_STREAM_W (widths 1 and n_stripes), which overrides it.
 static int env_stream_order() {
   static const int v = env_int("ECX_STREAM_ORDER", 0);
+  return v;
+}
+
+// ECX_STREAM_W: stripe-group width of the tile walk (stream_walk.h). N >= 1:
+// tiles are walked (group of N stripes, tile in chunk, stripe in group);
+// anything above the batch's stripe count means all of it. Unset: the width
+// ECX_STREAM_ORDER stands for.
+static int env_stream_w() {
+  static const int v = std::max(-1, env_int("ECX_STREAM_W", -1));
+  return v;
+}
+
+// ECX_STREAM_XCD: unset/1 = XCD-contiguous block mapping (each of the 8
+// compute dies walks one contiguous eighth of the tile order instead of every
+// 8th block of it), 0 = blocks in hardware order. Together with one tile per
+// block it is worth 3-5% on both legs at the flagship shape
+// (profiles/stream_walk_summary.md).
+static int env_stream_xcd() {
+  static const int v = env_int("ECX_STREAM_XCD", 1);
   return v;
 }
 
@@ -1633,7 +1649,7 @@ static int stream_grid(ecx_ctx* ctx, int n_out, uint64_t n_tiles,
   int bpc = env_stream_bpc();
   uint64_t g;
   if (bpc < 0) {
-    g = std::max<uint64_t>((uint64_t)cus * 8, (n_tiles + 1) / 2);
+    g = n_tiles;
   } else {
     if (bpc == 0) {
       bpc = ctx->stream_occ[n_out].load();
@@ -1695,18 +1711,17 @@ static int launch_stream(ecx_ctx* ctx, Slot& s, const uint8_t* d_buf,
   uint32_t grid = 1;
   int r = stream_grid(ctx, n_out, n_tiles, &grid);
   if (r != ECX_OK) return r;
-  const int order = env_stream_order() == 1 ? 1 : 0;
-  const uint32_t n_inner =
-      (uint32_t)std::max<uint64_t>(1, order ? (uint64_t)n_stripes : tpc);
-  const uint32_t n_outer = (uint32_t)(order ? tpc : (uint64_t)n_stripes);
-  const uint32_t step_q = grid / n_inner, step_r = grid % n_inner;
+  int width = env_stream_w();
+  if (width < 1) width = env_stream_order() == 1 ? (int)n_stripes : 1;
+  const EcxWalk walk =
+      ecx_walk_make((uint32_t)n_stripes, (uint32_t)std::max<uint64_t>(1, tpc),
+                    (uint32_t)width, env_stream_xcd() == 1, grid);
   const uint64_t stripe_bytes = (uint64_t)(ctx->k + ctx->m) * chunk_bytes;
 
   if (time_it) HIP_TRY(hipEventRecord(s.ev_start, s.stream));
   dispatch_nout(n_out, [&](auto NO) {
     hipLaunchKernelGGL((ec_gf_stream_kernel<NO()>), dim3(grid), dim3(256), 0,
-                       s.stream, d_buf, d_obuf, p, stripe_bytes, vecs,
-                       n_outer, n_inner, step_q, step_r, order);
+                       s.stream, d_buf, d_obuf, p, stripe_bytes, vecs, walk);
   });
   HIP_TRY(hipGetLastError());
   if (time_it) {
@@ -2743,6 +2758,29 @@ int ecx_gf8_tabs332_probe(uint8_t c, uint32_t out[5]) {
   if (!out) return ECX_ERR_INVAL;
   build_tabs332(ecx::gf8(), c, out);
   return ECX_OK;
+}
+
+int ecx_stream_walk_probe(uint32_t n_stripes, uint32_t tiles_per_chunk,
+                          uint32_t width, int xcd, uint32_t grid,
+                          uint32_t hw_block, uint32_t* stripes,
+                          uint32_t* tiles, int cap) {
+  if (n_stripes < 1 || n_stripes > 65535 || tiles_per_chunk < 1 ||
+      tiles_per_chunk >= 0x7fffffffu || grid < 1 || grid > (1u << 23) ||
+      hw_block >= grid || cap < 0 || (cap > 0 && (!stripes || !tiles)))
+    return ECX_ERR_INVAL;
+  const EcxWalk w = ecx_walk_make(n_stripes, tiles_per_chunk, width, xcd, grid);
+  long n = 0;
+  for (EcxWalkPos pos = ecx_walk_start(w, hw_block); ecx_walk_live(w, pos);
+       ecx_walk_next(w, pos)) {
+    const uint32_t stripe = ecx_walk_stripe(w, pos);
+    if (stripe >= n_stripes) continue;  // as the kernel skips it
+    if (n < cap) {
+      stripes[n] = stripe;
+      tiles[n] = pos.t;
+    }
+    if (++n > 0x7fffffffL) return ECX_ERR_INVAL;
+  }
+  return (int)n;
 }
 
 int ecx_matmul_batch(ecx_ctx* ctx, void* dptr, long n_stripes,

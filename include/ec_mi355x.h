@@ -268,6 +268,18 @@ ECX_API int ecx_decode_rows_probe(int technique, int k, int m,
  * x>>6 of out[4] (little-endian byte order) is c*x in GF(2^8). */
 ECX_API int ecx_gf8_tabs332_probe(uint8_t c, uint32_t out[5]);
 
+/* CPU-only probe of the streaming batch kernel's tile walk: the (stripe,
+ * tile in chunk) pairs that hardware block `hw_block` of a `grid`-block
+ * launch visits, in order, for a batch of n_stripes stripes of
+ * tiles_per_chunk 4 KiB tiles, under stripe-group width `width` (0 or more
+ * than n_stripes: all stripes) and, with xcd != 0, the XCD-contiguous block
+ * mapping. Runs the kernel's own start/step code. Writes at most `cap`
+ * pairs and returns how many the block visits, or -errno. */
+ECX_API int ecx_stream_walk_probe(uint32_t n_stripes, uint32_t tiles_per_chunk,
+                                  uint32_t width, int xcd, uint32_t grid,
+                                  uint32_t hw_block, uint32_t *stripes,
+                                  uint32_t *tiles, int cap);
+
 /* Generic device-batch GF(2^8) matmul over the standard batch layout:
  * out chunk ids = XOR_i rows[j*n_src+i] * src chunk ids, per stripe. The
  * composition primitive for layered codes (LRC layers, custom research

@@ -2,11 +2,16 @@
 // Answers: what does gfx950 HBM deliver for G-byte pieces strided S bytes
 // (the jerasure packet layout makes the bitmatrix kernel read 256 B
 // pieces at 2 KiB stride), vs contiguous streaming? Standalone; writes
-// one JSON line per pattern.
-//   hipcc --offload-arch=gfx950 -O3 tools/membench.hip -o gpurun_out/membench
+// one JSON line per pattern. `membench floor ...` (floor_main below) is the
+// streaming batch kernel's address pattern with no arithmetic.
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/membench.hip -o membench
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+
+#include "../ceph_amd/csrc/stream_walk.h"
 
 #define HT(x) do { hipError_t e = (x); if (e != hipSuccess) { \
   fprintf(stderr, "HIP %s\n", hipGetErrorString(e)); exit(1); } } while (0)
@@ -164,7 +169,140 @@ __global__ __launch_bounds__(256) void xor3_kernel(
   }
 }
 
-int main() {
+// ---- floor of the streaming batch kernel (ec_gf_stream_kernel): K reads
+// and m writes over the batch layout with the kernel's own tile walk
+// (stream_walk.h) and nothing else - no tables, no metadata, no GF(2^8)
+// arithmetic. Every lane issues its K nontemporal 16 B loads at once, XORs
+// them and issues m nontemporal 16 B stores of the result. Two arms:
+//   interleaved: the batch layout, stripe stride (K+m) C, chunk stride C
+//   chunk-major: the same bytes with each of the K+m streams contiguous,
+//                stripe stride C, chunk stride C S
+// The largest address either arm touches is below (K+m) C S.
+template <int K>
+__global__ __launch_bounds__(256, 8) void floor_kernel(
+    const uint8_t* buf, uint8_t* obuf, uint64_t stripe_stride,
+    uint64_t chunk_stride, uint64_t vecs_per_chunk, int m,
+    const EcxWalk walk) {
+  const uint32_t voff = threadIdx.x << 4;
+  for (EcxWalkPos pos = ecx_walk_start(walk, blockIdx.x);
+       ecx_walk_live(walk, pos); ecx_walk_next(walk, pos)) {
+    const uint32_t stripe = ecx_walk_stripe(walk, pos);
+    const uint32_t tile = pos.t;
+    if (stripe >= walk.n_stripes ||
+        ((uint64_t)tile << 8) + threadIdx.x >= vecs_per_chunk)
+      continue;
+    const uint64_t tbase =
+        (uint64_t)stripe * stripe_stride + ((uint64_t)tile << 12);
+    v4u d[K];
+#pragma unroll
+    for (int i = 0; i < K; i++)
+      d[i] = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(
+          buf + tbase + (uint64_t)i * chunk_stride + voff));
+    v4u acc = d[0];
+#pragma unroll
+    for (int i = 1; i < K; i++) {
+      acc.x ^= d[i].x; acc.y ^= d[i].y; acc.z ^= d[i].z; acc.w ^= d[i].w;
+    }
+    for (int j = 0; j < m; j++)
+      __builtin_nontemporal_store(
+          acc, reinterpret_cast<v4u*>(obuf + tbase +
+                                      (uint64_t)(K + j) * chunk_stride + voff));
+  }
+}
+
+template <int K>
+static void floor_launch(int k, uint32_t grid, uint8_t* d, uint64_t ss,
+                         uint64_t cs, uint64_t vecs, int m, const EcxWalk& w) {
+  if constexpr (K > 1) {
+    if (k != K) return floor_launch<K - 1>(k, grid, d, ss, cs, vecs, m, w);
+  }
+  hipLaunchKernelGGL(floor_kernel<K>, dim3(grid), dim3(256), 0, 0, d, d, ss,
+                     cs, vecs, m, w);
+}
+
+// One point: both arms, 2 warm-up and 7 timed launches each, median time.
+static void floor_point(uint8_t* d, int k, int m, long C, long S, long width,
+                        int xcd, long bpc, int cus, hipEvent_t* ev) {
+  const uint64_t vecs = (uint64_t)C >> 4, tpc = (vecs + 255) / 256;
+  const uint64_t n_tiles = tpc * (uint64_t)S;
+  // the grid rule of the library: bpc < 0 two tiles per block and no fewer
+  // than 8 blocks per CU, otherwise bpc blocks per CU (0: the 8 that stay
+  // resident)
+  uint64_t g = bpc < 0 ? std::max<uint64_t>((uint64_t)cus * 8, (n_tiles + 1) / 2)
+                       : (uint64_t)cus * (uint64_t)(bpc == 0 ? 8 : bpc);
+  g = std::max<uint64_t>(1, std::min<uint64_t>(std::min(g, n_tiles), 1ull << 23));
+  const EcxWalk w =
+      ecx_walk_make((uint32_t)S, (uint32_t)tpc, (uint32_t)width, xcd, (uint32_t)g);
+  const double bytes = (double)(k + m) * (double)C * (double)S;
+  for (int arm = 0; arm < 2; arm++) {
+    const uint64_t ss = arm ? (uint64_t)C : (uint64_t)(k + m) * C;
+    const uint64_t cs = arm ? (uint64_t)C * S : (uint64_t)C;
+    const int warm = 2, reps = 7;
+    float ms[reps];
+    for (int r = 0; r < warm + reps; r++) {
+      if (r >= warm) HT(hipEventRecord(ev[0]));
+      floor_launch<16>(k, (uint32_t)g, d, ss, cs, vecs, m, w);
+      HT(hipGetLastError());
+      if (r >= warm) {
+        HT(hipEventRecord(ev[1]));
+        HT(hipEventSynchronize(ev[1]));
+        HT(hipEventElapsedTime(&ms[r - warm], ev[0], ev[1]));
+      }
+    }
+    std::sort(ms, ms + reps);
+    printf("{\"pattern\": \"%s\", \"k\": %d, \"m\": %d, \"chunk\": %ld, "
+           "\"stripes\": %ld, \"W\": %u, \"xcd\": %d, \"bpc\": %ld, "
+           "\"grid\": %llu, \"ms_median\": %.4f, \"ms_min\": %.4f, "
+           "\"GBs\": %.0f}\n",
+           arm ? "floor-chunk-major" : "floor-interleaved", k, m, C, S,
+           w.width, xcd, bpc, (unsigned long long)g, ms[reps / 2], ms[0],
+           bytes / (ms[reps / 2] * 1e6));
+    fflush(stdout);
+  }
+}
+
+//   membench floor K M C S [W XCD BPC]   one point (defaults 1 0 -1)
+//   membench floor K M C S sweep         W x XCD x BPC of the walk sweep
+static int floor_main(int argc, char** argv) {
+  if (argc < 6) {
+    fprintf(stderr, "usage: membench floor K M C S [W XCD BPC | sweep]\n");
+    return 2;
+  }
+  const int k = atoi(argv[2]), m = atoi(argv[3]);
+  const long C = atol(argv[4]), S = atol(argv[5]);
+  if (k < 1 || k > 16 || m < 1 || m > 16 || C < 16 || C % 16 || S < 1 ||
+      S > 65535 || ((uint64_t)C >> 12) >= 0x7fffffffull) {
+    fprintf(stderr, "floor: need 1<=K,M<=16, C a multiple of 16, S<=65535\n");
+    return 2;
+  }
+  const size_t total = (size_t)(k + m) * (size_t)C * (size_t)S;
+  uint8_t* d;
+  HT(hipMalloc(&d, total));
+  HT(hipMemset(d, 0x5a, total));
+  hipDeviceProp_t prop;
+  HT(hipGetDeviceProperties(&prop, 0));
+  const int cus = std::max(1, prop.multiProcessorCount);
+  hipEvent_t ev[2];
+  HT(hipEventCreate(&ev[0]));
+  HT(hipEventCreate(&ev[1]));
+  if (argc > 6 && strcmp(argv[6], "sweep") == 0) {
+    const long widths[] = {1, 2, 4, 8, 16, 64, S};
+    const long bpcs[] = {-1, 4096, 1024};
+    for (long bpc : bpcs)
+      for (int xcd = 0; xcd < 2; xcd++)
+        for (long wd : widths) floor_point(d, k, m, C, S, wd, xcd, bpc, cus, ev);
+  } else {
+    const long wd = argc > 6 ? atol(argv[6]) : 1;
+    const int xcd = argc > 7 ? atoi(argv[7]) : 0;
+    const long bpc = argc > 8 ? atol(argv[8]) : -1;
+    floor_point(d, k, m, C, S, wd < 0 ? 0 : wd, xcd, bpc, cus, ev);
+  }
+  HT(hipFree(d));
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && strcmp(argv[1], "floor") == 0) return floor_main(argc, argv);
   const size_t total = 8ull << 30;  // 8 GiB working set
   uint8_t* d;
   uint32_t* sink;
