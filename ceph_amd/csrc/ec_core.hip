@@ -1060,10 +1060,6 @@ __global__ __launch_bounds__(256) void ec_fill_random_kernel(
 // Host-side: context, streams, decode-row LRU, launches
 // ---------------------------------------------------------------------------
 
-// bounded query-spin waits (defined in the host-pointer section below)
-static hipError_t wait_event(hipEvent_t ev);
-static hipError_t wait_stream(hipStream_t st);
-
 namespace {
 
 struct Slot {
@@ -1099,22 +1095,19 @@ struct Slot {
   std::recursive_mutex mu;
 };
 
+// Decode plan for one present mask, in the context's technique.
 struct DecodePlan {
   std::vector<int> survivors;
   std::vector<int> erased;
-  std::vector<uint8_t> rows;  // n_erased x k
+  // w=8: n_erased x k coefficients; bitmatrix: (n_erased*w) x (k*w) bits
+  std::vector<uint8_t> rows;
+  std::vector<uint16_t> rows16;  // w=16: n_erased x k u16
 };
 
-struct BitPlan {
-  std::vector<int> survivors;
-  std::vector<int> erased;
-  std::vector<uint8_t> rows;  // (n_erased*w) x (k*w) bits
-};
-
-struct Decode16Plan {
-  std::vector<int> survivors;
-  std::vector<int> erased;
-  std::vector<uint16_t> rows;  // n_erased x k u16
+// The rows of a coded job, in the context's technique.
+struct CodeRows {
+  const uint8_t* r8;    // w=8 coefficients, or bitmatrix bit rows
+  const uint16_t* r16;  // w=16 coefficients
 };
 
 }  // namespace
@@ -1133,8 +1126,6 @@ struct ecx_ctx {
   std::mutex lru_mu;
   std::map<uint64_t, std::pair<DecodePlan, std::list<uint64_t>::iterator>> lru;
   std::list<uint64_t> lru_order;
-  std::map<uint64_t, BitPlan> bit_lru;  // bitmatrix decode plans
-  std::map<uint64_t, Decode16Plan> lru16;  // w=16 decode plans
   static constexpr size_t LRU_DEPTH = 4096;
   // host-pointer calls round-robin the stream slots so concurrent plugin
   // threads (the OSD's PG workers) overlap instead of serialising on one
@@ -1151,6 +1142,13 @@ struct ecx_ctx {
            technique == ECX_T_CAUCHY_GOOD_JERASURE;
   }
   bool is_w16() const { return technique == ECX_T_RS_VAN_JERASURE_W16; }
+  bool is_table8() const { return !is_w16() && !is_bitmatrix(); }
+  // the coding rows of the generator
+  CodeRows gen_rows() const {
+    if (is_bitmatrix()) return {bitmat.data(), nullptr};
+    if (is_w16()) return {nullptr, gen16.data() + (size_t)k * k};
+    return {gen.data() + (size_t)k * k, nullptr};
+  }
 };
 
 static int map_hip(hipError_t e) {
@@ -1443,10 +1441,63 @@ static void fill_params(EcLaunchParams* p, const int* src_ids, int n_src,
   fill_rec(p, src_ids, n_src, out_ids, n_out, coeff, src_null);
 }
 
+// Chunk ids of a job whose sources lead the stripe: 0..n_src-1, the outputs
+// behind them (an encode: data, then parity).
+static void stripe_ids(int n_src, int n_out, int* src_ids, int* out_ids) {
+  for (int i = 0; i < n_src; i++) src_ids[i] = i;
+  for (int j = 0; j < n_out; j++) out_ids[j] = n_src + j;
+}
+
 // Knobs are read once per process (A/B-able via env on the GPU box).
 static int env_int(const char* name, int dflt) {
   const char* e = getenv(name);
   return e ? atoi(e) : dflt;
+}
+
+// The same for byte counts, which need not fit an int.
+static size_t env_size(const char* name, size_t dflt) {
+  const char* e = getenv(name);
+  return e ? (size_t)std::max(0L, atol(e)) : dflt;
+}
+
+// Blocking hipEventSynchronize/hipStreamSynchronize park the thread in
+// the driver (~37 us each measured on MI355X, r1 profiles) — ruinous for
+// sub-ms host calls (the OSD's real call shape is many small calls,
+// ECUtil.cc:485-514). A bounded hipEventQuery/hipStreamQuery spin costs
+// ~1-2 us when the work is already done or finishes soon; fall back to
+// the blocking wait after ~500 us so large calls still park politely.
+// ECX_SPINWAIT=0 disables.
+static int env_spinwait() {
+  static const int v = env_int("ECX_SPINWAIT", 1);
+  return v;
+}
+
+static hipError_t wait_event(hipEvent_t ev) {
+  if (env_spinwait()) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (;;) {
+      hipError_t e = hipEventQuery(ev);
+      if (e != hipErrorNotReady) return e;
+      if (std::chrono::steady_clock::now() - t0 >
+          std::chrono::microseconds(500))
+        break;
+    }
+  }
+  return hipEventSynchronize(ev);
+}
+
+static hipError_t wait_stream(hipStream_t st) {
+  if (env_spinwait()) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (;;) {
+      hipError_t e = hipStreamQuery(st);
+      if (e != hipErrorNotReady) return e;
+      if (std::chrono::steady_clock::now() - t0 >
+          std::chrono::microseconds(500))
+        break;
+    }
+  }
+  return hipStreamSynchronize(st);
 }
 
 // ECX_NT=1 (nontemporal loads/stores) measured +7% encode bandwidth —
@@ -2219,43 +2270,37 @@ static int run_matmul16(ecx_ctx* ctx, int slot_i, const uint8_t* d_buf,
   return ECX_OK;
 }
 
-// Decode plan for a mask from `cache` (w=16 and bitmatrix plans: cleared
-// when full), composed by compose(plan) on a miss.
-template <class Plan, class Compose>
-static int get_cached_plan(ecx_ctx* ctx, std::map<uint64_t, Plan>& cache,
-                           uint64_t present_mask, Plan& out,
-                           Compose&& compose) {
-  std::lock_guard<std::mutex> g(ctx->lru_mu);
-  auto it = cache.find(present_mask);
-  if (it != cache.end()) {
-    out = it->second;
+// Apply rows (n_out x n_src, in the context's technique) to the stripes of
+// d_buf in place: the one technique dispatch of the batch and the
+// host-pointer calls. src_null marks zeros-chunk sources for the w=8
+// kernels; the other two read every source. time_it goes to the bitmatrix
+// and w=16 launchers; run_matmul always times its first group.
+static int run_coded(ecx_ctx* ctx, int slot_i, uint8_t* d_buf,
+                     const int* src_ids, int n_src, const int* out_ids,
+                     int n_out, CodeRows rows, const bool* src_null,
+                     long n_stripes, size_t chunk_bytes, bool time_it) {
+  if (slot_i < 0 || slot_i >= (int)ctx->slots.size()) return ECX_ERR_INVAL;
+  if (ctx->is_bitmatrix()) {
+    const size_t out_bits = (size_t)ctx->w * n_src * ctx->w;  // per output
+    for (int j0 = 0; j0 < n_out; j0 += ECX_MAX_OUT) {
+      int r = run_bitmatrix(ctx, slot_i, d_buf, d_buf, src_ids, n_src,
+                            out_ids + j0, std::min(ECX_MAX_OUT, n_out - j0),
+                            rows.r8 + j0 * out_bits, n_stripes, chunk_bytes,
+                            time_it);
+      if (r != ECX_OK) return r;
+    }
     return ECX_OK;
   }
-  Plan plan;
-  if (!compose(plan)) return ECX_ERR_IO;
-  if (cache.size() > ecx_ctx::LRU_DEPTH) cache.clear();
-  cache.emplace(present_mask, plan);
-  out = plan;
-  return ECX_OK;
+  if (ctx->is_w16())
+    return run_matmul16(ctx, slot_i, d_buf, d_buf, src_ids, n_src, out_ids,
+                        n_out, rows.r16, n_stripes, chunk_bytes, false,
+                        time_it);
+  return run_matmul(ctx, slot_i, d_buf, d_buf, src_ids, n_src, out_ids, n_out,
+                    rows.r8, src_null, n_stripes, chunk_bytes, false);
 }
 
-static int get_plan16(ecx_ctx* ctx, uint64_t present_mask,
-                      Decode16Plan& out) {
-  return get_cached_plan(ctx, ctx->lru16, present_mask, out, [&](auto& p) {
-    return ecx::compose_decode_rows16(ctx->gen16, ctx->k, ctx->m,
-                                      present_mask, p.survivors, p.erased,
-                                      p.rows);
-  });
-}
-
-static int get_bit_plan(ecx_ctx* ctx, uint64_t present_mask, BitPlan& out) {
-  return get_cached_plan(ctx, ctx->bit_lru, present_mask, out, [&](auto& p) {
-    return ecx::compose_bit_decode_rows(ctx->bitmat, ctx->k, ctx->m, ctx->w,
-                                        present_mask, p.survivors, p.erased,
-                                        p.rows);
-  });
-}
-
+// Decode plan for a mask through the context's LRU, composed for the
+// context's technique on a miss.
 static int get_decode_plan(ecx_ctx* ctx, uint64_t present_mask,
                            DecodePlan& out) {
   std::lock_guard<std::mutex> g(ctx->lru_mu);
@@ -2268,9 +2313,19 @@ static int get_decode_plan(ecx_ctx* ctx, uint64_t present_mask,
     return ECX_OK;
   }
   DecodePlan plan;
-  if (!ecx::compose_decode_rows(ctx->gen, ctx->k, ctx->m, present_mask,
-                                plan.survivors, plan.erased, plan.rows))
-    return ECX_ERR_IO;
+  const int k = ctx->k, m = ctx->m;
+  const bool ok =
+      ctx->is_w16()
+          ? ecx::compose_decode_rows16(ctx->gen16, k, m, present_mask,
+                                       plan.survivors, plan.erased,
+                                       plan.rows16)
+      : ctx->is_bitmatrix()
+          ? ecx::compose_bit_decode_rows(ctx->bitmat, k, m, ctx->w,
+                                         present_mask, plan.survivors,
+                                         plan.erased, plan.rows)
+          : ecx::compose_decode_rows(ctx->gen, k, m, present_mask,
+                                     plan.survivors, plan.erased, plan.rows);
+  if (!ok) return ECX_ERR_IO;
   ctx->lru_order.push_front(present_mask);
   ctx->lru.emplace(present_mask,
                    std::make_pair(plan, ctx->lru_order.begin()));
@@ -2324,59 +2379,32 @@ extern "C" {
 int ecx_encode_batch(ecx_ctx* ctx, void* dptr, long n_stripes,
                      size_t chunk_bytes, int slot) {
   if (!ctx || !dptr) return ECX_ERR_INVAL;
-  int k = ctx->k, m = ctx->m;
+  // the bitmatrix batch calls take their outputs in one launch
+  if (ctx->is_bitmatrix() && ctx->m > ECX_MAX_OUT) return ECX_ERR_INVAL;
   int src_ids[ECX_MAX_K], out_ids[ECX_MAX_K];
-  for (int i = 0; i < k; i++) src_ids[i] = i;
-  for (int j = 0; j < m; j++) out_ids[j] = k + j;
-  if (ctx->is_bitmatrix()) {
-    if (slot < 0 || slot >= (int)ctx->slots.size()) return ECX_ERR_INVAL;
-    return run_bitmatrix(ctx, slot, (const uint8_t*)dptr, (uint8_t*)dptr,
-                         src_ids, k, out_ids, m, ctx->bitmat.data(),
-                         n_stripes, chunk_bytes, true);
-  }
-  if (ctx->is_w16())
-    return run_matmul16(ctx, slot, (const uint8_t*)dptr, (uint8_t*)dptr,
-                        src_ids, k, out_ids, m,
-                        ctx->gen16.data() + (size_t)k * k, n_stripes,
-                        chunk_bytes, false, true);
-  const uint8_t* rows = ctx->gen.data() + (size_t)k * k;
-  return run_matmul(ctx, slot, (const uint8_t*)dptr, (uint8_t*)dptr, src_ids,
-                    k, out_ids, m, rows, nullptr, n_stripes, chunk_bytes,
-                    false);
+  stripe_ids(ctx->k, ctx->m, src_ids, out_ids);
+  return run_coded(ctx, slot, (uint8_t*)dptr, src_ids, ctx->k, out_ids,
+                   ctx->m, ctx->gen_rows(), nullptr, n_stripes, chunk_bytes,
+                   /*time_it=*/true);
 }
 
 int ecx_decode_batch(ecx_ctx* ctx, void* dptr, long n_stripes,
                      size_t chunk_bytes, uint64_t present_mask, int slot) {
   if (!ctx || !dptr) return ECX_ERR_INVAL;
-  if (ctx->is_bitmatrix()) {
-    if (slot < 0 || slot >= (int)ctx->slots.size()) return ECX_ERR_INVAL;
-    BitPlan plan;
-    int r = get_bit_plan(ctx, present_mask, plan);
-    if (r != ECX_OK) return r;
-    if (plan.erased.empty()) return ECX_OK;
-    return run_bitmatrix(ctx, slot, (const uint8_t*)dptr, (uint8_t*)dptr,
-                         plan.survivors.data(), ctx->k, plan.erased.data(),
-                         (int)plan.erased.size(), plan.rows.data(),
-                         n_stripes, chunk_bytes, /*time_it=*/true);
-  }
-  if (ctx->is_w16()) {
-    Decode16Plan plan;
-    int r = get_plan16(ctx, present_mask, plan);
-    if (r != ECX_OK) return r;
-    if (plan.erased.empty()) return ECX_OK;
-    return run_matmul16(ctx, slot, (const uint8_t*)dptr, (uint8_t*)dptr,
-                        plan.survivors.data(), ctx->k, plan.erased.data(),
-                        (int)plan.erased.size(), plan.rows.data(),
-                        n_stripes, chunk_bytes, false, /*time_it=*/true);
-  }
+  // a bad slot is refused before the plan, as it always was for bitmatrix
+  if (ctx->is_bitmatrix() && (slot < 0 || slot >= (int)ctx->slots.size()))
+    return ECX_ERR_INVAL;
   DecodePlan plan;
   int r = get_decode_plan(ctx, present_mask, plan);
   if (r != ECX_OK) return r;
   if (plan.erased.empty()) return ECX_OK;
-  return run_matmul(ctx, slot, (const uint8_t*)dptr, (uint8_t*)dptr,
-                    plan.survivors.data(), ctx->k, plan.erased.data(),
-                    (int)plan.erased.size(), plan.rows.data(), nullptr,
-                    n_stripes, chunk_bytes, false);
+  // the bitmatrix batch calls take their outputs in one launch
+  if (ctx->is_bitmatrix() && plan.erased.size() > ECX_MAX_OUT)
+    return ECX_ERR_INVAL;
+  return run_coded(ctx, slot, (uint8_t*)dptr, plan.survivors.data(), ctx->k,
+                   plan.erased.data(), (int)plan.erased.size(),
+                   {plan.rows.data(), plan.rows16.data()}, nullptr, n_stripes,
+                   chunk_bytes, /*time_it=*/true);
 }
 
 int ecx_encode_delta_dev(ecx_ctx* ctx, const void* d_old, const void* d_new,
@@ -2444,8 +2472,7 @@ int ecx_encode_slices(ecx_ctx* ctx, void* const* d_chunks,
     return ECX_ERR_INVAL;
   int k = ctx->k, m = ctx->m;
   int src_ids[ECX_MAX_K], out_ids[ECX_MAX_K];
-  for (int i = 0; i < k; i++) src_ids[i] = i;
-  for (int j = 0; j < m; j++) out_ids[j] = k + j;
+  stripe_ids(k, m, src_ids, out_ids);
   return run_slices(ctx, slot, d_chunks, bytes, n_slices, src_ids, k,
                     out_ids, m, ctx->gen.data() + (size_t)k * k);
 }
@@ -2631,15 +2658,6 @@ int ecx_decode_multi_plan_probe(int technique, int k, int m,
   return (int)grp.launches.size();
 }
 
-// defined in the host-pointer section below
-static int ensure_stage(ecx_ctx* ctx, Slot& s, size_t bytes);
-static int env_hostpipe();
-static int pipelined_matmul_host(ecx_ctx* ctx, Slot& s,
-                                 const uint8_t* const* srcs, int n_src,
-                                 uint8_t* const* outs, int n_out,
-                                 const uint8_t* rows, size_t chunk_bytes,
-                                 int cache_kind = 0);
-
 int ecx_set_matrix(ecx_ctx* ctx, const uint8_t* coding_rows) {
   if (!ctx || !coding_rows || ctx->is_bitmatrix() || ctx->is_w16())
     return ECX_ERR_INVAL;
@@ -2657,53 +2675,7 @@ int ecx_set_matrix(ecx_ctx* ctx, const uint8_t* coding_rows) {
               (size_t)ctx->m * ctx->k);
   ctx->lru.clear();
   ctx->lru_order.clear();
-  ctx->bit_lru.clear();
-  ctx->lru16.clear();
   for (auto& s : ctx->slots) s.pparams_kind = 0;  // resident tables stale
-  return ECX_OK;
-}
-
-int ecx_matmul_chunks_host(ecx_ctx* ctx, const uint8_t* const* srcs,
-                           int n_src, uint8_t* const* outs, int n_out,
-                           const uint8_t* rows, size_t bytes) {
-  if (!ctx || !srcs || !outs || !rows || n_src < 1 || n_src > ECX_MAX_K ||
-      n_out < 1 || n_out > ECX_MAX_K || bytes % 16)
-    return ECX_ERR_INVAL;
-  Slot& s = ctx->slots[ctx->rr++ % ctx->slots.size()];
-  std::lock_guard<std::recursive_mutex> g(s.mu);
-  if (env_hostpipe())
-    return pipelined_matmul_host(ctx, s, srcs, n_src, outs, n_out, rows,
-                                 bytes);
-  int r = ensure_stage(ctx, s, (size_t)(n_src + n_out) * bytes);
-  if (r != ECX_OK) return r;
-  HIP_TRY(hipSetDevice(ctx->device));
-  bool src_null[ECX_MAX_K] = {};
-  for (int i = 0; i < n_src; i++) {
-    if (!srcs[i]) {
-      src_null[i] = true;
-      continue;
-    }
-    HIP_TRY(hipMemcpyAsync(s.d_stage + (size_t)i * bytes, srcs[i], bytes,
-                           hipMemcpyHostToDevice, s.stream));
-  }
-  int src_ids[ECX_MAX_K], out_ids[ECX_MAX_K];
-  for (int i = 0; i < n_src; i++) src_ids[i] = i;
-  for (int j = 0; j < n_out; j++) out_ids[j] = n_src + j;
-  for (int j0 = 0; j0 < n_out; j0 += 4) {
-    int nj = std::min(4, n_out - j0);
-    EcLaunchParams p;
-    fill_params(&p, src_ids, n_src, out_ids + j0, nj,
-                rows + (size_t)j0 * n_src, src_null);
-    int rr = launch_matmul(ctx, s, s.d_stage, s.d_stage, p, 1, bytes, false,
-                           false);
-    if (rr != ECX_OK) return rr;
-  }
-  for (int j = 0; j < n_out; j++) {
-    if (!outs[j]) continue;
-    HIP_TRY(hipMemcpyAsync(outs[j], s.d_stage + (size_t)(n_src + j) * bytes,
-                           bytes, hipMemcpyDeviceToHost, s.stream));
-  }
-  HIP_TRY(wait_stream(s.stream));
   return ECX_OK;
 }
 
@@ -2823,48 +2795,66 @@ int ecx_last_kernel_ms(ecx_ctx* ctx, int slot, double* ms) {
 }  // extern "C"
 
 // ---- host-pointer (plugin) path ----
+// A call is described once (HostJob) and handed to host_call, which picks
+// one of three stagers: pipelined tiles (w=8 table rows), single-shot pinned
+// (w16 and bitmatrix up to ECX_HPIPE_MAX), or the legacy per-chunk copies
+// (ECX_HOSTPIPE=0, and w16/bitmatrix above ECX_HPIPE_MAX).
 
-// Blocking hipEventSynchronize/hipStreamSynchronize park the thread in
-// the driver (~37 us each measured on MI355X, r1 profiles) — ruinous for
-// sub-ms host calls (the OSD's real call shape is many small calls,
-// ECUtil.cc:485-514). A bounded hipEventQuery/hipStreamQuery spin costs
-// ~1-2 us when the work is already done or finishes soon; fall back to
-// the blocking wait after ~500 us so large calls still park politely.
-// ECX_SPINWAIT=0 disables.
-static int env_spinwait() {
-  static const int v = [] {
-    const char* e = getenv("ECX_SPINWAIT");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
+struct HostJob {
+  const uint8_t* src[ECX_MAX_K];  // NULL = zeros chunk
+  uint8_t* out[ECX_MAX_K];        // NULL = do not scatter (encode only)
+  // chunk position in the stripe buffer and chunk id of the launch. The
+  // pipelined stager packs its tiles itself: sources first, outputs behind.
+  int src_slot[ECX_MAX_K], out_slot[ECX_MAX_K];
+  int n_src, n_out, n_slots;
+  size_t chunk_bytes;
+  CodeRows rows;
+  // rows.r8 are GF(2^8) coefficients for the table kernel, whatever the
+  // context's technique (ecx_matmul_chunks_host)
+  bool table8;
+  int cache_kind;  // see pparams_kind; 1 only for the full encode
+};
+
+// Job over packed chunks, rows from the generator (encode) or the caller.
+static void job_from_rows(HostJob& job, const uint8_t* const* srcs, int n_src,
+                          uint8_t* const* outs, int n_out, CodeRows rows,
+                          bool table8, size_t chunk_bytes, int cache_kind) {
+  std::copy(srcs, srcs + n_src, job.src);
+  std::copy(outs, outs + n_out, job.out);
+  stripe_ids(n_src, n_out, job.src_slot, job.out_slot);
+  job.n_src = n_src;
+  job.n_out = n_out;
+  job.n_slots = n_src + n_out;
+  job.chunk_bytes = chunk_bytes;
+  job.rows = rows;
+  job.table8 = table8;
+  job.cache_kind = cache_kind;
 }
 
-static hipError_t wait_event(hipEvent_t ev) {
-  if (env_spinwait()) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-      hipError_t e = hipEventQuery(ev);
-      if (e != hipErrorNotReady) return e;
-      if (std::chrono::steady_clock::now() - t0 >
-          std::chrono::microseconds(500))
-        break;
-    }
+// Decode job: the plan's survivors rebuild its erased chunks, each at its
+// own position in the stripe. A NULL survivor is a zeros source
+// (ErasureCodeIsa.cc:212-226); an erased chunk is written, so it needs a
+// buffer.
+static int job_from_plan(const ecx_ctx* ctx, const DecodePlan& plan,
+                         uint8_t* const* chunks, size_t chunk_bytes,
+                         HostJob& job) {
+  job.n_src = ctx->k;
+  job.n_out = (int)plan.erased.size();
+  job.n_slots = ctx->k + ctx->m;
+  for (int i = 0; i < job.n_src; i++) {
+    job.src_slot[i] = plan.survivors[i];
+    job.src[i] = chunks[plan.survivors[i]];
   }
-  return hipEventSynchronize(ev);
-}
-
-static hipError_t wait_stream(hipStream_t st) {
-  if (env_spinwait()) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-      hipError_t e = hipStreamQuery(st);
-      if (e != hipErrorNotReady) return e;
-      if (std::chrono::steady_clock::now() - t0 >
-          std::chrono::microseconds(500))
-        break;
-    }
+  for (int j = 0; j < job.n_out; j++) {
+    job.out_slot[j] = plan.erased[j];
+    job.out[j] = chunks[plan.erased[j]];
+    if (!job.out[j]) return ECX_ERR_INVAL;
   }
-  return hipStreamSynchronize(st);
+  job.chunk_bytes = chunk_bytes;
+  job.rows = {plan.rows.data(), plan.rows16.data()};
+  job.table8 = ctx->is_table8();
+  job.cache_kind = 0;
+  return ECX_OK;
 }
 
 static int ensure_stage(ecx_ctx* ctx, Slot& s, size_t bytes) {
@@ -2893,25 +2883,19 @@ static int ensure_stage(ecx_ctx* ctx, Slot& s, size_t bytes) {
 // copy threads.
 
 static int env_hostpipe() {
-  static const int v = [] {
-    const char* e = getenv("ECX_HOSTPIPE");
-    return e ? atoi(e) : 1;
-  }();
+  static const int v = env_int("ECX_HOSTPIPE", 1);
   return v;
 }
 
 static size_t env_hpipe_tile() {
-  static const size_t v = [] {
-    const char* e = getenv("ECX_HPIPE_TILE");
-    // 4 MiB default: the tile sweeps (profiles/rocprof_r01_summary.md)
-    // showed throughput monotonically rising with tile size at every
-    // chunk size tried — per-tile event syncs (~37 us each) cost more
-    // than cross-tile overlap buys, so prefer single-shot staging up to
-    // 4 MiB/chunk (pinned buffer: 2 x (k+m) x tile, grown on demand)
-    long x = e ? atol(e) : (4 << 20);
-    if (x < (16 << 10)) x = 16 << 10;
-    return (size_t)x & ~(size_t)15;
-  }();
+  // 4 MiB default: the tile sweeps (profiles/rocprof_r01_summary.md)
+  // showed throughput monotonically rising with tile size at every
+  // chunk size tried — per-tile event syncs (~37 us each) cost more
+  // than cross-tile overlap buys, so prefer single-shot staging up to
+  // 4 MiB/chunk (pinned buffer: 2 x (k+m) x tile, grown on demand)
+  static const size_t v =
+      std::max<size_t>(env_size("ECX_HPIPE_TILE", 4 << 20), 16 << 10) &
+      ~(size_t)15;
   return v;
 }
 
@@ -2976,8 +2960,7 @@ class CopyPool {
   };
 
   CopyPool() {
-    const char* e = getenv("ECX_HPIPE_THREADS");
-    int x = e ? atoi(e) : 7;  // helpers; the caller is the +1
+    int x = env_int("ECX_HPIPE_THREADS", 7);  // helpers; the caller is the +1
     n_workers_ = x < 0 ? 0 : (x > 63 ? 63 : x);
     for (int i = 0; i < n_workers_; i++)
       workers_.emplace_back([this] { loop(); });
@@ -3106,11 +3089,8 @@ static int ensure_pparams(ecx_ctx* ctx, Slot& s) {
 }
 
 static size_t env_hpipe_max() {
-  static const size_t v = [] {
-    const char* e = getenv("ECX_HPIPE_MAX");
-    long x = e ? atol(e) : (256L << 20);
-    return (size_t)(x < (1 << 20) ? (1 << 20) : x);
-  }();
+  static const size_t v =
+      std::max<size_t>(env_size("ECX_HPIPE_MAX", (size_t)256 << 20), 1 << 20);
   return v;
 }
 
@@ -3121,51 +3101,47 @@ static size_t env_hpipe_max() {
 // per-output D2H, scatter. Same measured rationale as
 // pipelined_matmul_host: per-chunk pageable copies pay ~50 us each.
 // Caller holds the slot lock and bounds the size by env_hpipe_max().
-template <class LaunchFn>
-static int staged_host_call(ecx_ctx* ctx, Slot& s,
-                            const uint8_t* const* hsrc, const int* src_slot,
-                            int n_src, uint8_t* const* hout,
-                            const int* out_slot, int n_out, int n_slots,
-                            size_t chunk_bytes, LaunchFn&& launch) {
-  int r = ensure_pipe(ctx, s, (size_t)n_slots * chunk_bytes);
+static int staged_host_call(ecx_ctx* ctx, int slot_i, const HostJob& job) {
+  Slot& s = ctx->slots[slot_i];
+  const size_t cb = job.chunk_bytes;
+  int r = ensure_pipe(ctx, s, (size_t)job.n_slots * cb);
   if (r != ECX_OK) return r;
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(wait_event(s.ev_pipe[0]));
   HIP_TRY(wait_event(s.ev_pipe[1]));
   std::vector<CopyOp> ops;
-  int lo = n_slots, hi = 0;
-  for (int i = 0; i < n_src; i++) {
-    const int sl = src_slot[i];
+  int lo = job.n_slots, hi = 0;
+  for (int i = 0; i < job.n_src; i++) {
+    const int sl = job.src_slot[i];
     lo = std::min(lo, sl);
     hi = std::max(hi, sl + 1);
-    if (hsrc[i])
-      ops.push_back({s.h_pipe + (size_t)sl * chunk_bytes, hsrc[i],
-                     chunk_bytes});
+    if (job.src[i])
+      ops.push_back({s.h_pipe + (size_t)sl * cb, job.src[i], cb});
     else
-      std::memset(s.h_pipe + (size_t)sl * chunk_bytes, 0, chunk_bytes);
+      std::memset(s.h_pipe + (size_t)sl * cb, 0, cb);
   }
   par_copy(ops);
-  HIP_TRY(hipMemcpyAsync(s.d_pipe + (size_t)lo * chunk_bytes,
-                         s.h_pipe + (size_t)lo * chunk_bytes,
-                         (size_t)(hi - lo) * chunk_bytes,
+  HIP_TRY(hipMemcpyAsync(s.d_pipe + (size_t)lo * cb,
+                         s.h_pipe + (size_t)lo * cb, (size_t)(hi - lo) * cb,
                          hipMemcpyHostToDevice, s.stream));
-  r = launch(s.d_pipe);
+  // the launchers keep per-call param staging, so no tiling
+  r = run_coded(ctx, slot_i, s.d_pipe, job.src_slot, job.n_src, job.out_slot,
+                job.n_out, job.rows, nullptr, 1, cb, false);
   if (r != ECX_OK) {
     (void)hipStreamSynchronize(s.stream);  // quiesce before buffer reuse
     return r;
   }
-  for (int j = 0; j < n_out; j++) {
-    if (!hout[j]) continue;
-    HIP_TRY(hipMemcpyAsync(s.h_pipe + (size_t)out_slot[j] * chunk_bytes,
-                           s.d_pipe + (size_t)out_slot[j] * chunk_bytes,
-                           chunk_bytes, hipMemcpyDeviceToHost, s.stream));
+  for (int j = 0; j < job.n_out; j++) {
+    if (!job.out[j]) continue;
+    HIP_TRY(hipMemcpyAsync(s.h_pipe + (size_t)job.out_slot[j] * cb,
+                           s.d_pipe + (size_t)job.out_slot[j] * cb, cb,
+                           hipMemcpyDeviceToHost, s.stream));
   }
   HIP_TRY(wait_stream(s.stream));
   ops.clear();
-  for (int j = 0; j < n_out; j++)
-    if (hout[j])
-      ops.push_back({hout[j], s.h_pipe + (size_t)out_slot[j] * chunk_bytes,
-                     chunk_bytes});
+  for (int j = 0; j < job.n_out; j++)
+    if (job.out[j])
+      ops.push_back({job.out[j], s.h_pipe + (size_t)job.out_slot[j] * cb, cb});
   par_copy(ops);
   return ECX_OK;
 }
@@ -3173,11 +3149,12 @@ static int staged_host_call(ecx_ctx* ctx, Slot& s,
 // Generic host-pointer matmul (w=8 table techniques): srcs[i] == NULL is
 // the zeros-chunk convention (skipped via cls), outs[j] == NULL skips the
 // scatter of that output. Caller holds the slot lock.
-static int pipelined_matmul_host(ecx_ctx* ctx, Slot& s,
-                                 const uint8_t* const* srcs, int n_src,
-                                 uint8_t* const* outs, int n_out,
-                                 const uint8_t* rows, size_t chunk_bytes,
-                                 int cache_kind) {
+static int pipelined_matmul_host(ecx_ctx* ctx, Slot& s, const HostJob& job) {
+  const uint8_t* const* srcs = job.src;
+  uint8_t* const* outs = job.out;
+  const int n_src = job.n_src, n_out = job.n_out;
+  const uint8_t* rows = job.rows.r8;
+  const size_t chunk_bytes = job.chunk_bytes;
   if (n_src < 1 || n_src > ECX_MAX_K || n_out < 1 || n_out > ECX_MAX_K ||
       !chunk_bytes || chunk_bytes % 16)
     return ECX_ERR_INVAL;
@@ -3192,8 +3169,25 @@ static int pipelined_matmul_host(ecx_ctx* ctx, Slot& s,
   bool src_null[ECX_MAX_K] = {};
   for (int i = 0; i < n_src; i++) src_null[i] = (srcs[i] == nullptr);
   int src_ids[ECX_MAX_K], out_ids[ECX_MAX_K];
-  for (int i = 0; i < n_src; i++) src_ids[i] = i;
-  for (int j = 0; j < n_out; j++) out_ids[j] = n_src + j;
+  stripe_ids(n_src, n_out, src_ids, out_ids);
+
+  // one tile's sources into hbuf packed at tl spacing, and its outputs back
+  // out of it; off is the tile's offset in the chunks
+  std::vector<CopyOp> ops;
+  ops.reserve(cps);
+  auto gather = [&](uint8_t* hbuf, size_t off, size_t tl) {
+    ops.clear();
+    for (int i = 0; i < n_src; i++)
+      if (srcs[i]) ops.push_back({hbuf + (size_t)i * tl, srcs[i] + off, tl});
+    par_copy(ops);
+  };
+  auto scatter = [&](const uint8_t* hbuf, size_t off, size_t tl) {
+    ops.clear();
+    for (int j = 0; j < n_out; j++)
+      if (outs[j])
+        ops.push_back({outs[j] + off, hbuf + ((size_t)n_src + j) * tl, tl});
+    par_copy(ops);
+  };
 
   // coefficient tables are tile-invariant: build and upload them ONCE,
   // then every tile's kernels reference the resident copies. For the hot
@@ -3205,7 +3199,8 @@ static int pipelined_matmul_host(ecx_ctx* ctx, Slot& s,
   if (groups > 8) return ECX_ERR_INVAL;
   bool any_null = false;
   for (int i = 0; i < n_src; i++) any_null |= src_null[i];
-  const int want_kind = (cache_kind != 0 && !any_null) ? cache_kind : 0;
+  const int want_kind =
+      (job.cache_kind != 0 && !any_null) ? job.cache_kind : 0;
   if (want_kind == 0 || s.pparams_kind != want_kind) {
     // a previous successful call drained both pipe events, but an errored
     // one may not have: make the pinned param area provably safe to rewrite
@@ -3235,28 +3230,19 @@ static int pipelined_matmul_host(ecx_ctx* ctx, Slot& s,
   // and the captured work is content-independent, so the graph stays
   // valid across calls and across param-table rewrites. ECX_HGRAPH=0
   // disables. (DESIGN: the OSD call shape is many small calls.)
-  static const int env_hg = [] {
-    const char* e = getenv("ECX_HGRAPH");
-    return e ? atoi(e) : 1;
-  }();
+  static const int env_hg = env_int("ECX_HGRAPH", 1);
   // Graph replay wins where per-call submit overhead dominates and loses
   // where hipGraphLaunch's runtime serialisation bites (measured, one
   // box: 64 KiB x1 +25%, 64 KiB x8 callers -12%, 256 KiB x1 -9%,
   // 1 MiB x8 -21%). Default: small calls only.
-  static const size_t env_hg_max = [] {
-    const char* e = getenv("ECX_HGRAPH_MAX");
-    return e ? (size_t)atol(e) : (size_t)(128 << 10);
-  }();
+  static const size_t env_hg_max = env_size("ECX_HGRAPH_MAX", 128 << 10);
   if (T == 1 && env_hg && chunk_bytes <= env_hg_max) {
     const size_t tl = chunk_bytes;
     uint8_t* hbuf = s.h_pipe;
     uint8_t* dbuf = s.d_pipe;
     HIP_TRY(wait_event(s.ev_pipe[0]));
     HIP_TRY(wait_event(s.ev_pipe[1]));
-    std::vector<CopyOp> gops;
-    for (int i = 0; i < n_src; i++)
-      if (srcs[i]) gops.push_back({hbuf + (size_t)i * tl, srcs[i], tl});
-    par_copy(gops);
+    gather(hbuf, 0, tl);
     const uint64_t key =
         (uint64_t)tl | ((uint64_t)n_src << 44) | ((uint64_t)n_out << 52);
     auto it = s.graphs.find(key);
@@ -3295,17 +3281,11 @@ static int pipelined_matmul_host(ecx_ctx* ctx, Slot& s,
     HIP_TRY(hipGraphLaunch(it->second, s.stream));
     HIP_TRY(hipEventRecord(s.ev_pipe[0], s.stream));
     HIP_TRY(wait_event(s.ev_pipe[0]));
-    gops.clear();
-    for (int j = 0; j < n_out; j++)
-      if (outs[j])
-        gops.push_back({outs[j], hbuf + ((size_t)n_src + j) * tl, tl});
-    par_copy(gops);
+    scatter(hbuf, 0, tl);
     return ECX_OK;
   }
 
   size_t tl_of[2] = {0, 0}, off_of[2] = {0, 0};
-  std::vector<CopyOp> ops;
-  ops.reserve(cps);
   for (long t = 0; t < T; t++) {
     const int b = (int)(t & 1);
     const size_t off = (size_t)t * TS;
@@ -3315,23 +3295,13 @@ static int pipelined_matmul_host(ecx_ctx* ctx, Slot& s,
     // buffer b holds tile t-2 until its D2H lands; wait, scatter it out,
     // then refill — the CPU work here overlaps tile t-1's DMA + kernels
     HIP_TRY(wait_event(s.ev_pipe[b]));
-    if (t >= 2) {
-      ops.clear();
-      for (int j = 0; j < n_out; j++)
-        if (outs[j])
-          ops.push_back({outs[j] + off_of[b],
-                         hbuf + ((size_t)n_src + j) * tl_of[b], tl_of[b]});
-      par_copy(ops);
-    }
+    if (t >= 2) scatter(hbuf, off_of[b], tl_of[b]);
     // gather tile t's sources packed at tl spacing (gaps where srcs[i] is
     // NULL are never read: cls==0 skips those sources in the kernel), then
     // ONE H2D DMA. Per-source interleaved copy+DMA was measured SLOWER
     // (15.3 vs 19.0 GiB/s at 1 MiB chunks): the extra DMA submissions and
     // OpenMP fork/joins cost more than the overlap hides.
-    ops.clear();
-    for (int i = 0; i < n_src; i++)
-      if (srcs[i]) ops.push_back({hbuf + (size_t)i * tl, srcs[i] + off, tl});
-    par_copy(ops);
+    gather(hbuf, off, tl);
     HIP_TRY(hipMemcpyAsync(dbuf, hbuf, (size_t)n_src * tl,
                            hipMemcpyHostToDevice, s.stream));
     const MatmulCfg c = matmul_cfg((long)(tl >> 4), 1);
@@ -3355,15 +3325,74 @@ static int pipelined_matmul_host(ecx_ctx* ctx, Slot& s,
   for (long t = std::max(0L, T - 2); t < T; t++) {
     const int b = (int)(t & 1);
     HIP_TRY(wait_event(s.ev_pipe[b]));
-    uint8_t* hbuf = s.h_pipe + (size_t)b * cps * TS;
-    ops.clear();
-    for (int j = 0; j < n_out; j++)
-      if (outs[j])
-        ops.push_back({outs[j] + off_of[b],
-                       hbuf + ((size_t)n_src + j) * tl_of[b], tl_of[b]});
-    par_copy(ops);
+    scatter(s.h_pipe + (size_t)b * cps * TS, off_of[b], tl_of[b]);
   }
   return ECX_OK;
+}
+
+// Legacy per-chunk staging, every technique: one pageable hipMemcpyAsync per
+// source into the slot's stage buffer, the launches, one copy per output,
+// then wait. A zeros-chunk source is skipped by class mask for the w=8 table
+// kernel and materialised in the stage buffer for w16 and bitmatrix, which
+// read every source. Caller holds the slot lock.
+static int legacy_host_call(ecx_ctx* ctx, int slot_i, const HostJob& job) {
+  Slot& s = ctx->slots[slot_i];
+  const size_t cb = job.chunk_bytes;
+  int r = ensure_stage(ctx, s, (size_t)job.n_slots * cb);
+  if (r != ECX_OK) return r;
+  HIP_TRY(hipSetDevice(ctx->device));
+  bool src_null[ECX_MAX_K] = {};
+  for (int i = 0; i < job.n_src; i++) {
+    uint8_t* d = s.d_stage + (size_t)job.src_slot[i] * cb;
+    if (job.src[i])
+      HIP_TRY(hipMemcpyAsync(d, job.src[i], cb, hipMemcpyHostToDevice,
+                             s.stream));
+    else if (job.table8)
+      src_null[i] = true;  // zeros chunk (ErasureCodeJerasure.cc:146-157)
+    else
+      HIP_TRY(hipMemsetAsync(d, 0, cb, s.stream));
+  }
+  if (job.table8) {
+    // the table kernel, as this path always launched (run_matmul may pick
+    // the stream kernel)
+    for (int j0 = 0; j0 < job.n_out && r == ECX_OK; j0 += 4) {
+      EcLaunchParams p;
+      fill_params(&p, job.src_slot, job.n_src, job.out_slot + j0,
+                  std::min(4, job.n_out - j0),
+                  job.rows.r8 + (size_t)j0 * job.n_src, src_null);
+      r = launch_matmul(ctx, s, s.d_stage, s.d_stage, p, 1, cb, false, false);
+    }
+  } else {
+    r = run_coded(ctx, slot_i, s.d_stage, job.src_slot, job.n_src,
+                  job.out_slot, job.n_out, job.rows, nullptr, 1, cb, false);
+  }
+  if (r != ECX_OK) {
+    (void)hipStreamSynchronize(s.stream);  // quiesce before buffer reuse
+    return r;
+  }
+  for (int j = 0; j < job.n_out; j++) {
+    if (!job.out[j]) continue;
+    HIP_TRY(hipMemcpyAsync(job.out[j],
+                           s.d_stage + (size_t)job.out_slot[j] * cb, cb,
+                           hipMemcpyDeviceToHost, s.stream));
+  }
+  HIP_TRY(wait_stream(s.stream));
+  return ECX_OK;
+}
+
+// Run a host job on slot slot_i (lock held by the caller) through the stager
+// for its rows and size. Arguments the launchers would refuse only after
+// copies were enqueued are refused here.
+static int host_call(ecx_ctx* ctx, int slot_i, const HostJob& job) {
+  if (!job.table8 && ctx->is_bitmatrix() &&
+      (job.chunk_bytes == 0 ||
+       job.chunk_bytes % ((size_t)ctx->w * ctx->pkt)))
+    return ECX_ERR_INVAL;
+  if (!env_hostpipe()) return legacy_host_call(ctx, slot_i, job);
+  if (job.table8) return pipelined_matmul_host(ctx, ctx->slots[slot_i], job);
+  if ((size_t)job.n_slots * job.chunk_bytes <= env_hpipe_max())
+    return staged_host_call(ctx, slot_i, job);
+  return legacy_host_call(ctx, slot_i, job);
 }
 
 extern "C" {
@@ -3371,270 +3400,41 @@ extern "C" {
 int ecx_encode_chunks_host(ecx_ctx* ctx, const uint8_t* const* data,
                            uint8_t* const* parity, size_t chunk_bytes) {
   if (!ctx || !data || !parity || chunk_bytes % 16) return ECX_ERR_INVAL;
-  int k = ctx->k, m = ctx->m;
   const int si = (int)(ctx->rr++ % ctx->slots.size());
-  Slot& s = ctx->slots[si];
-  std::lock_guard<std::recursive_mutex> g(s.mu);
-  if (!ctx->is_w16() && !ctx->is_bitmatrix() && env_hostpipe())
-    return pipelined_matmul_host(ctx, s, data, k, parity, m,
-                                 ctx->gen.data() + (size_t)k * k,
-                                 chunk_bytes, /*cache_kind=*/1);
-  if (env_hostpipe() && (size_t)(k + m) * chunk_bytes <= env_hpipe_max()) {
-    // w16 / bitmatrix: single-shot pinned staging around the technique's
-    // own launcher (they keep per-call param staging, so no tiling)
-    int src_ids[ECX_MAX_K], out_ids[ECX_MAX_K];
-    for (int i = 0; i < k; i++) src_ids[i] = i;
-    for (int j = 0; j < m; j++) out_ids[j] = k + j;
-    return staged_host_call(
-        ctx, s, data, src_ids, k, parity, out_ids, m, k + m, chunk_bytes,
-        [&](uint8_t* d) -> int {
-          if (ctx->is_w16())
-            return run_matmul16(ctx, si, d, d, src_ids, k, out_ids, m,
-                                ctx->gen16.data() + (size_t)k * k, 1,
-                                chunk_bytes, false, false);
-          for (int j0 = 0; j0 < m; j0 += ECX_MAX_OUT) {
-            int nj = std::min(ECX_MAX_OUT, m - j0);
-            int rr = run_bitmatrix(
-                ctx, si, d, d, src_ids, k, out_ids + j0, nj,
-                ctx->bitmat.data() + (size_t)(j0 * ctx->w) * k * ctx->w, 1,
-                chunk_bytes, false);
-            if (rr != ECX_OK) return rr;
-          }
-          return ECX_OK;
-        });
-  }
-  int r = ensure_stage(ctx, s, (size_t)(k + m) * chunk_bytes);
-  if (r != ECX_OK) return r;
-  HIP_TRY(hipSetDevice(ctx->device));
-  bool src_null[ECX_MAX_K] = {};
-  for (int i = 0; i < k; i++) {
-    if (!data[i]) {
-      src_null[i] = true;  // zeros chunk (ErasureCodeJerasure.cc:146-157)
-      continue;
-    }
-    HIP_TRY(hipMemcpyAsync(s.d_stage + (size_t)i * chunk_bytes, data[i],
-                           chunk_bytes, hipMemcpyHostToDevice, s.stream));
-  }
-  int src_ids[ECX_MAX_K], out_ids[ECX_MAX_K];
-  for (int i = 0; i < k; i++) src_ids[i] = i;
-  for (int j = 0; j < m; j++) out_ids[j] = k + j;
-  if (ctx->is_w16()) {
-    // per-slice NULL handled via cls in run_matmul16? no: zero-fill stage
-    for (int i = 0; i < k; i++)
-      if (src_null[i])
-        HIP_TRY(hipMemsetAsync(s.d_stage + (size_t)i * chunk_bytes, 0,
-                               chunk_bytes, s.stream));
-    int rr = run_matmul16(ctx, si, s.d_stage, s.d_stage, src_ids, k,
-                          out_ids, m, ctx->gen16.data() + (size_t)k * k, 1,
-                          chunk_bytes, false, false);
-    if (rr != ECX_OK) return rr;
-  } else if (ctx->is_bitmatrix()) {
-    // zeros-chunk convention: materialise zeros in the stage buffer
-    for (int i = 0; i < k; i++)
-      if (src_null[i])
-        HIP_TRY(hipMemsetAsync(s.d_stage + (size_t)i * chunk_bytes, 0,
-                               chunk_bytes, s.stream));
-    for (int j0 = 0; j0 < m; j0 += ECX_MAX_OUT) {
-      int nj = std::min(ECX_MAX_OUT, m - j0);
-      int rr = run_bitmatrix(
-          ctx, si, s.d_stage, s.d_stage, src_ids, k, out_ids + j0, nj,
-          ctx->bitmat.data() + (size_t)(j0 * ctx->w) * k * ctx->w, 1,
-          chunk_bytes, false);
-      if (rr != ECX_OK) return rr;
-    }
-  } else {
-  const uint8_t* rows = ctx->gen.data() + (size_t)k * k;
-  for (int j0 = 0; j0 < m; j0 += 4) {
-    int nj = std::min(4, m - j0);
-    EcLaunchParams p;
-    fill_params(&p, src_ids, k, out_ids + j0, nj, rows + (size_t)j0 * k,
-                src_null);
-    int rr = launch_matmul(ctx, s, s.d_stage, s.d_stage, p, 1, chunk_bytes,
-                           false, false);
-    if (rr != ECX_OK) return rr;
-  }
-  }
-  for (int j = 0; j < m; j++) {
-    if (!parity[j]) continue;
-    HIP_TRY(hipMemcpyAsync(parity[j], s.d_stage + (size_t)(k + j) * chunk_bytes,
-                           chunk_bytes, hipMemcpyDeviceToHost, s.stream));
-  }
-  HIP_TRY(wait_stream(s.stream));
-  return ECX_OK;
+  std::lock_guard<std::recursive_mutex> g(ctx->slots[si].mu);
+  HostJob job;
+  job_from_rows(job, data, ctx->k, parity, ctx->m, ctx->gen_rows(),
+                ctx->is_table8(), chunk_bytes, /*cache_kind=*/1);
+  return host_call(ctx, si, job);
 }
 
 int ecx_decode_chunks_host(ecx_ctx* ctx, uint8_t* const* chunks,
                            uint64_t present_mask, size_t chunk_bytes) {
   if (!ctx || !chunks || chunk_bytes % 16) return ECX_ERR_INVAL;
-  int k = ctx->k, m = ctx->m, n = k + m;
-
-  if (ctx->is_w16()) {
-    Decode16Plan plan;
-    int r = get_plan16(ctx, present_mask, plan);
-    if (r != ECX_OK) return r;
-    if (plan.erased.empty()) return ECX_OK;
-    const int si = (int)(ctx->rr++ % ctx->slots.size());
-    Slot& s = ctx->slots[si];
-    std::lock_guard<std::recursive_mutex> g(s.mu);
-    if (env_hostpipe() && (size_t)n * chunk_bytes <= env_hpipe_max()) {
-      const int ne = (int)plan.erased.size();
-      const uint8_t* srcs[ECX_MAX_K];
-      uint8_t* douts[ECX_MAX_K];
-      for (int i = 0; i < k; i++) srcs[i] = chunks[plan.survivors[i]];
-      for (int j = 0; j < ne; j++) {
-        if (!chunks[plan.erased[j]]) return ECX_ERR_INVAL;
-        douts[j] = chunks[plan.erased[j]];
-      }
-      return staged_host_call(
-          ctx, s, srcs, plan.survivors.data(), k, douts,
-          plan.erased.data(), ne, n, chunk_bytes, [&](uint8_t* d) {
-            return run_matmul16(ctx, si, d, d, plan.survivors.data(), k,
-                                plan.erased.data(), ne, plan.rows.data(),
-                                1, chunk_bytes, false, false);
-          });
-    }
-    r = ensure_stage(ctx, s, (size_t)n * chunk_bytes);
-    if (r != ECX_OK) return r;
-    HIP_TRY(hipSetDevice(ctx->device));
-    for (int i = 0; i < k; i++) {
-      int id = plan.survivors[i];
-      if (!chunks[id]) {
-        HIP_TRY(hipMemsetAsync(s.d_stage + (size_t)id * chunk_bytes, 0,
-                               chunk_bytes, s.stream));
-        continue;
-      }
-      HIP_TRY(hipMemcpyAsync(s.d_stage + (size_t)id * chunk_bytes,
-                             chunks[id], chunk_bytes, hipMemcpyHostToDevice,
-                             s.stream));
-    }
-    r = run_matmul16(ctx, si, s.d_stage, s.d_stage, plan.survivors.data(),
-                     k, plan.erased.data(), (int)plan.erased.size(),
-                     plan.rows.data(), 1, chunk_bytes, false, false);
-    if (r != ECX_OK) return r;
-    for (int e : plan.erased) {
-      if (!chunks[e]) return ECX_ERR_INVAL;
-      HIP_TRY(hipMemcpyAsync(chunks[e], s.d_stage + (size_t)e * chunk_bytes,
-                             chunk_bytes, hipMemcpyDeviceToHost, s.stream));
-    }
-    HIP_TRY(wait_stream(s.stream));
-    return ECX_OK;
-  }
-
-  if (ctx->is_bitmatrix()) {
-    BitPlan plan;
-    int r = get_bit_plan(ctx, present_mask, plan);
-    if (r != ECX_OK) return r;
-    if (plan.erased.empty()) return ECX_OK;
-    const int si = (int)(ctx->rr++ % ctx->slots.size());
-    Slot& s = ctx->slots[si];
-    std::lock_guard<std::recursive_mutex> g(s.mu);
-    if (env_hostpipe() && (size_t)n * chunk_bytes <= env_hpipe_max()) {
-      const int ne = (int)plan.erased.size();
-      const uint8_t* srcs[ECX_MAX_K];
-      uint8_t* douts[ECX_MAX_K];
-      for (int i = 0; i < k; i++) srcs[i] = chunks[plan.survivors[i]];
-      for (int j = 0; j < ne; j++) {
-        if (!chunks[plan.erased[j]]) return ECX_ERR_INVAL;
-        douts[j] = chunks[plan.erased[j]];
-      }
-      return staged_host_call(
-          ctx, s, srcs, plan.survivors.data(), k, douts,
-          plan.erased.data(), ne, n, chunk_bytes, [&](uint8_t* d) -> int {
-            for (int j0 = 0; j0 < ne; j0 += ECX_MAX_OUT) {
-              int nj = std::min(ECX_MAX_OUT, ne - j0);
-              int rr = run_bitmatrix(
-                  ctx, si, d, d, plan.survivors.data(), k,
-                  plan.erased.data() + j0, nj,
-                  plan.rows.data() + (size_t)j0 * ctx->w * k * ctx->w, 1,
-                  chunk_bytes, false);
-              if (rr != ECX_OK) return rr;
-            }
-            return ECX_OK;
-          });
-    }
-    r = ensure_stage(ctx, s, (size_t)n * chunk_bytes);
-    if (r != ECX_OK) return r;
-    HIP_TRY(hipSetDevice(ctx->device));
-    for (int i = 0; i < k; i++) {
-      int id = plan.survivors[i];
-      if (!chunks[id]) {
-        HIP_TRY(hipMemsetAsync(s.d_stage + (size_t)id * chunk_bytes, 0,
-                               chunk_bytes, s.stream));
-        continue;
-      }
-      HIP_TRY(hipMemcpyAsync(s.d_stage + (size_t)id * chunk_bytes,
-                             chunks[id], chunk_bytes, hipMemcpyHostToDevice,
-                             s.stream));
-    }
-    for (size_t j0 = 0; j0 < plan.erased.size(); j0 += ECX_MAX_OUT) {
-      int nj = (int)std::min<size_t>(ECX_MAX_OUT, plan.erased.size() - j0);
-      int rr = run_bitmatrix(
-          ctx, si, s.d_stage, s.d_stage, plan.survivors.data(), k,
-          plan.erased.data() + j0, nj,
-          plan.rows.data() + j0 * (size_t)ctx->w * k * ctx->w, 1,
-          chunk_bytes, false);
-      if (rr != ECX_OK) return rr;
-    }
-    for (int e : plan.erased) {
-      if (!chunks[e]) return ECX_ERR_INVAL;
-      HIP_TRY(hipMemcpyAsync(chunks[e], s.d_stage + (size_t)e * chunk_bytes,
-                             chunk_bytes, hipMemcpyDeviceToHost, s.stream));
-    }
-    HIP_TRY(wait_stream(s.stream));
-    return ECX_OK;
-  }
-
   DecodePlan plan;
   int r = get_decode_plan(ctx, present_mask, plan);
   if (r != ECX_OK) return r;
   if (plan.erased.empty()) return ECX_OK;
-
-  Slot& s = ctx->slots[ctx->rr++ % ctx->slots.size()];
-  std::lock_guard<std::recursive_mutex> g(s.mu);
-  if (env_hostpipe()) {
-    const uint8_t* srcs[ECX_MAX_K];
-    uint8_t* douts[ECX_MAX_K];
-    for (int i = 0; i < k; i++)
-      srcs[i] = chunks[plan.survivors[i]];  // NULL => zeros source
-                                            // (ErasureCodeIsa.cc:212-226)
-    const int ne = (int)plan.erased.size();
-    for (int j = 0; j < ne; j++) {
-      if (!chunks[plan.erased[j]]) return ECX_ERR_INVAL;
-      douts[j] = chunks[plan.erased[j]];
-    }
-    return pipelined_matmul_host(ctx, s, srcs, k, douts, ne,
-                                 plan.rows.data(), chunk_bytes);
-  }
-  r = ensure_stage(ctx, s, (size_t)n * chunk_bytes);
+  const int si = (int)(ctx->rr++ % ctx->slots.size());
+  std::lock_guard<std::recursive_mutex> g(ctx->slots[si].mu);
+  HostJob job;
+  r = job_from_plan(ctx, plan, chunks, chunk_bytes, job);
   if (r != ECX_OK) return r;
-  HIP_TRY(hipSetDevice(ctx->device));
-  bool src_null[ECX_MAX_K] = {};
-  for (int i = 0; i < k; i++) {
-    int id = plan.survivors[i];
-    if (!chunks[id]) {
-      src_null[i] = true;  // present-but-absent buffer => zeros
-                           // (ErasureCodeIsa.cc:212-226)
-      continue;
-    }
-    HIP_TRY(hipMemcpyAsync(s.d_stage + (size_t)id * chunk_bytes, chunks[id],
-                           chunk_bytes, hipMemcpyHostToDevice, s.stream));
-  }
-  for (size_t j0 = 0; j0 < plan.erased.size(); j0 += 4) {
-    int nj = (int)std::min<size_t>(4, plan.erased.size() - j0);
-    EcLaunchParams p;
-    fill_params(&p, plan.survivors.data(), k, plan.erased.data() + j0, nj,
-                plan.rows.data() + j0 * k, src_null);
-    int rr = launch_matmul(ctx, s, s.d_stage, s.d_stage, p, 1, chunk_bytes,
-                           false, false);
-    if (rr != ECX_OK) return rr;
-  }
-  for (int e : plan.erased) {
-    if (!chunks[e]) return ECX_ERR_INVAL;
-    HIP_TRY(hipMemcpyAsync(chunks[e], s.d_stage + (size_t)e * chunk_bytes,
-                           chunk_bytes, hipMemcpyDeviceToHost, s.stream));
-  }
-  HIP_TRY(wait_stream(s.stream));
-  return ECX_OK;
+  return host_call(ctx, si, job);
+}
+
+int ecx_matmul_chunks_host(ecx_ctx* ctx, const uint8_t* const* srcs,
+                           int n_src, uint8_t* const* outs, int n_out,
+                           const uint8_t* rows, size_t bytes) {
+  if (!ctx || !srcs || !outs || !rows || n_src < 1 || n_src > ECX_MAX_K ||
+      n_out < 1 || n_out > ECX_MAX_K || bytes % 16)
+    return ECX_ERR_INVAL;
+  const int si = (int)(ctx->rr++ % ctx->slots.size());
+  std::lock_guard<std::recursive_mutex> g(ctx->slots[si].mu);
+  HostJob job;
+  job_from_rows(job, srcs, n_src, outs, n_out, {rows, nullptr},
+                /*table8=*/true, bytes, /*cache_kind=*/0);
+  return host_call(ctx, si, job);
 }
 
 int ecx_encode_delta_host(ecx_ctx* ctx, const uint8_t* old_data,
