@@ -101,6 +101,19 @@ def _lib():
         ctypes.c_int, ctypes.c_int, ctypes.c_int,
         ctypes.POINTER(ctypes.c_uint64), ctypes.c_long,
         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    lib.ecx_update_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_long, ctypes.c_size_t,
+                                     ctypes.c_void_p,
+                                     ctypes.POINTER(ctypes.c_uint64),
+                                     ctypes.c_int]
+    lib.ecx_update_plan_probe.argtypes = [
+        ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64),
+        ctypes.c_long, ctypes.POINTER(ctypes.c_long),
+        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    lib.ecx_apply_deltas_host.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
+        ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
+        ctypes.c_int, ctypes.c_size_t]
     lib.ecx_set_matrix.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.ecx_matmul_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_long, ctypes.c_size_t,
@@ -228,6 +241,23 @@ def decode_multi_plan_probe(technique, k, m, masks):
         pos.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
         ctypes.byref(n_plans)), "ecx_decode_multi_plan_probe")
     return r, pos[:len(a)], n_plans.value
+
+
+def update_plan_probe(k, m, masks):
+    """CPU-only: how update_batch would prepare these per-stripe write
+    masks. Returns (n_launches, new_base, active): new_base[s] is the index
+    of stripe s's first new chunk in the packed d_new, active the ascending
+    stripes with a nonzero mask."""
+    a = _mask_array(masks, len(masks), "ecx_update_plan_probe")
+    base = np.zeros(max(len(a), 1), dtype=np.int64)
+    act = np.zeros(max(len(a), 1), dtype=np.int32)
+    n_act = ctypes.c_int()
+    r = _ck(lib().ecx_update_plan_probe(
+        k, m, _u64p(a), len(a),
+        base.ctypes.data_as(ctypes.POINTER(ctypes.c_long)),
+        act.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+        ctypes.byref(n_act)), "ecx_update_plan_probe")
+    return r, base[:len(a)], act[:n_act.value]
 
 
 def _ptr_array(bufs):
@@ -361,6 +391,17 @@ class EcContext:
         _ck(lib().ecx_decode_slices_multi(self._h, arr, sz, n, _u64p(a),
                                           slot), "ecx_decode_slices_multi")
 
+    def update_batch(self, dptr, n_stripes, chunk_bytes, d_new, write_masks,
+                     slot=0):
+        """Parity-delta write over a batch: write_masks[s] bit j = data
+        chunk j of stripe s is replaced by its new content from the packed
+        device buffer d_new (stripe ascending, then chunk id ascending);
+        every parity of a touched stripe is corrected in place. ceil(m/4)
+        launches whatever the masks are."""
+        a = _mask_array(write_masks, n_stripes, "ecx_update_batch")
+        _ck(lib().ecx_update_batch(self._h, dptr, n_stripes, chunk_bytes,
+                                   d_new, _u64p(a), slot), "ecx_update_batch")
+
     def matmul_batch(self, dptr, n_stripes, chunk_bytes, src_ids, out_ids,
                      rows, slot=0):
         """Generic device-batch GF matmul over chunk ids (LRC layer
@@ -437,3 +478,21 @@ class EcContext:
             coding_shard, parity.ctypes.data_as(ctypes.c_void_p),
             delta.nbytes), "ecx_apply_delta_host")
         return parity
+
+    def apply_deltas(self, deltas, parities):
+        """Fused apply_delta: deltas {data shard id: uint8 array}, parities
+        {coding shard id: uint8 array}. Every parity is corrected in place
+        by every delta in one staged call; returns parities."""
+        ds, cs = sorted(deltas), sorted(parities)
+        sizes = {a.nbytes for a in deltas.values()} | \
+                {a.nbytes for a in parities.values()}
+        if len(sizes) > 1:
+            raise EcError("ecx_apply_deltas_host: equal-length buffers "
+                          f"required, got sizes {sorted(sizes)}")
+        _ck(lib().ecx_apply_deltas_host(
+            self._h, _ptr_array([deltas[i] for i in ds]),
+            (ctypes.c_int * len(ds))(*ds), len(ds),
+            _ptr_array([parities[j] for j in cs]),
+            (ctypes.c_int * len(cs))(*cs), len(cs),
+            sizes.pop() if sizes else 0), "ecx_apply_deltas_host")
+        return parities

@@ -48,6 +48,7 @@
 #include "../../include/ec_mi355x.h"
 #include "gf.h"
 #include "decode_multi.h"
+#include "update_plan.h"
 #include "stream_walk.h"
 
 // ---------------------------------------------------------------------------
@@ -496,6 +497,82 @@ __global__ __launch_bounds__(256, 2) void ec_gf_slices_multi_kernel(
   ecx_slices_body<NOUT, NT>(chunk_ptrs, block_slice, block_voff, slice_vecs,
                             cps, vecs_per_block, n_src, s_tabs, s_src, s_out,
                             s_cls);
+}
+
+// ---- parity-delta writes over a batch (ecx_update_batch) ----
+// A write queue overwrites a different set of data chunks in every stripe:
+// P_r ^= G[k+r][j] * (old_j ^ new_j) for each written chunk j, then chunk j
+// takes its new content (matrix_apply_delta over the batch,
+// ErasureCodeJerasure.cc:285-331 / ErasureCodeIsa.cc:333-366). The record is
+// the ENCODE record of one <= 4-parity pass (k sources), the same for every
+// stripe; a block resolves blockIdx.y -> active[y] -> stripe -> write mask
+// and stages only the columns of the chunks its stripe writes, so the source
+// loop is popcount(mask) long and unwritten data chunks are never read.
+// cls stays wave-uniform because the staged record is per block.
+//
+// The data stores alias the old-data loads (same address, same lane, load
+// first) and the parity stores alias the parity loads, so buf carries no
+// __restrict__; d_new lies outside the batch (checked by the host). The
+// delta cannot be re-formed once the old data is gone: with m > 4 only the
+// last pass (LAST) stores the new data, earlier passes read old and new
+// again and leave the data alone.
+template <int NOUT, bool NT, bool LAST>
+__global__ __launch_bounds__(256, 2) void ec_gf_update_kernel(
+    uint8_t* buf, const uint8_t* __restrict__ d_new,
+    const EcMultiRec* __restrict__ rec,        // this pass, k sources
+    const uint64_t* __restrict__ write_masks,  // [n_stripes]
+    const int* __restrict__ new_base,          // [n_stripes]
+    const int* __restrict__ active,            // [gridDim.y]
+    int k, long chunk_bytes, int chunks_per_stripe, long vecs_per_chunk) {
+  __shared__ uint32_t s_tabs[ECX_MULTI_OUT * ECX_MAX_K * 6];
+  __shared__ int s_src[ECX_MAX_K];
+  __shared__ int s_out[ECX_MULTI_OUT];
+  __shared__ uint8_t s_cls[ECX_MULTI_OUT * ECX_MAX_K];
+  const long stripe = active[blockIdx.y];
+  const uint32_t mask = (uint32_t)write_masks[stripe];  // bits < k <= 32
+  const int n_src = __builtin_popcount(mask);
+  const unsigned nthr = blockDim.x;
+  // one (output j, written chunk t) column per thread: at most 4 * 32
+  for (int c = threadIdx.x; c < NOUT * n_src; c += nthr) {
+    const int j = c / n_src, t = c - j * n_src;
+    uint32_t rest = mask;
+    for (int i = 0; i < t; i++) rest &= rest - 1;  // drop the t lowest bits
+    const int id = __builtin_ctz(rest);
+    const uint32_t* T = &rec->tabs[(j * k + id) * 6];
+#pragma unroll
+    for (int q = 0; q < 6; q++) s_tabs[c * 6 + q] = T[q];
+    s_cls[c] = rec->cls[j * k + id];
+    if (j == 0) s_src[t] = id;
+  }
+  for (int t = threadIdx.x; t < NOUT; t += nthr) s_out[t] = rec->out_ids[t];
+  __syncthreads();
+
+  uint8_t* sb = buf + stripe * chunks_per_stripe * chunk_bytes;
+  const uint8_t* nb = d_new + (long)new_base[stripe] * chunk_bytes;
+  for (long p = (long)blockIdx.x * nthr + threadIdx.x; p < vecs_per_chunk;
+       p += (long)gridDim.x * nthr) {
+    const long off = p << 4;
+    // the body is short (one or two sources): parity and the first source's
+    // two loads are all in flight before the first use
+    v4u acc[NOUT];
+#pragma unroll
+    for (int j = 0; j < NOUT; j++)
+      acc[j] = ecx_ld16<NT>(sb + (long)s_out[j] * chunk_bytes + off);
+    v4u old = ecx_ld16<NT>(sb + (long)s_src[0] * chunk_bytes + off);
+    v4u nw = ecx_ld16<NT>(nb + off);
+    for (int t = 0; t < n_src; t++) {
+      const v4u d = old ^ nw, keep = nw;
+      if (t + 1 < n_src) {
+        old = ecx_ld16<NT>(sb + (long)s_src[t + 1] * chunk_bytes + off);
+        nw = ecx_ld16<NT>(nb + (long)(t + 1) * chunk_bytes + off);
+      }
+      ecx_gf_source<NOUT>(s_tabs, s_cls, n_src, t, d, acc);
+      if (LAST) ecx_st16<NT>(sb + (long)s_src[t] * chunk_bytes + off, keep);
+    }
+#pragma unroll
+    for (int j = 0; j < NOUT; j++)
+      ecx_st16<NT>(sb + (long)s_out[j] * chunk_bytes + off, acc[j]);
+  }
 }
 
 // ---- GF(2^16) (w=16 jerasure RS-van) path ----
@@ -2339,6 +2416,7 @@ static int get_decode_plan(ecx_ctx* ctx, uint64_t present_mask,
 
 // ---- per-stripe erasure patterns: host side ----
 static_assert(ECX_MULTI_OUT == ecx::MULTI_MAX_OUT, "kernel/grouping split");
+static_assert(ECX_MULTI_OUT == ecx::UPDATE_MAX_OUT, "kernel/update-plan split");
 static_assert(sizeof(EcMultiRec) % 8 == 0, "8-byte arrays follow the table");
 
 // Group a call's masks (decode_multi.h) and fetch every distinct mask's
@@ -2656,6 +2734,100 @@ int ecx_decode_multi_plan_probe(int technique, int k, int m,
   std::memcpy(plan_of_stripe, grp.plan_of_stripe.data(), (size_t)n * 4);
   *n_plans = (int)grp.masks.size();
   return (int)grp.launches.size();
+}
+
+int ecx_update_batch(ecx_ctx* ctx, void* dptr, long n_stripes,
+                     size_t chunk_bytes, const void* d_new,
+                     const uint64_t* write_masks, int slot) {
+  if (!ctx || !dptr || !d_new || !write_masks || slot < 0 ||
+      slot >= (int)ctx->slots.size() || ctx->is_bitmatrix() ||
+      ctx->is_w16() || chunk_bytes == 0 || chunk_bytes % 16 ||
+      n_stripes <= 0 || n_stripes > 65535)
+    return ECX_ERR_INVAL;
+  const int k = ctx->k, m = ctx->m, cps = k + m;
+  // every mask is checked before anything is staged
+  ecx::UpdatePlan plan;
+  if (!ecx::plan_update(k, m, write_masks, n_stripes, plan))
+    return ECX_ERR_INVAL;
+  // the new chunks are read while the batch is written: no overlap
+  const uintptr_t b0 = (uintptr_t)dptr, n0 = (uintptr_t)d_new;
+  const uintptr_t b1 = b0 + (uintptr_t)n_stripes * cps * chunk_bytes;
+  const uintptr_t n1 = n0 + (uintptr_t)plan.total_new * chunk_bytes;
+  if (n0 < b1 && b0 < n1) return ECX_ERR_INVAL;
+  if (plan.launches == 0) return ECX_OK;  // nothing written anywhere
+
+  Slot& s = ctx->slots[slot];
+  std::lock_guard<std::recursive_mutex> g(s.mu);
+  HIP_TRY(hipSetDevice(ctx->device));
+
+  // blob: [encode record per pass][write_masks u64][new_base i32][active i32]
+  const int n_pass = plan.launches;
+  const size_t n_act = plan.active.size();
+  const size_t off_mask = (size_t)n_pass * sizeof(EcMultiRec);
+  const size_t off_base = off_mask + (size_t)n_stripes * 8;
+  const size_t off_act = off_base + (size_t)n_stripes * 4;
+  const size_t blob = off_act + n_act * 4;
+  int r = ensure_jobs(ctx, s, blob);
+  if (r != ECX_OK) return r;
+  HIP_TRY(wait_event(s.ev_jobs));
+  {
+    EcMultiRec* recs = (EcMultiRec*)s.h_jobs;
+    std::memset(recs, 0, off_mask);
+    int src_ids[ECX_MAX_K], out_ids[ECX_MAX_K];
+    stripe_ids(k, m, src_ids, out_ids);
+    const uint8_t* rows = ctx->gen.data() + (size_t)k * k;
+    for (int p = 0; p < n_pass; p++)
+      fill_rec(&recs[p], src_ids, k, out_ids + p * ECX_MULTI_OUT,
+               std::min(ECX_MULTI_OUT, m - p * ECX_MULTI_OUT),
+               rows + (size_t)p * ECX_MULTI_OUT * k, nullptr);
+  }
+  std::memcpy(s.h_jobs + off_mask, write_masks, (size_t)n_stripes * 8);
+  std::memcpy(s.h_jobs + off_base, plan.new_base.data(),
+              (size_t)n_stripes * 4);
+  std::memcpy(s.h_jobs + off_act, plan.active.data(), n_act * 4);
+  HIP_TRY(hipMemcpyAsync(s.d_jobs, s.h_jobs, blob, hipMemcpyHostToDevice,
+                         s.stream));
+  HIP_TRY(hipEventRecord(s.ev_jobs, s.stream));
+
+  const EcMultiRec* d_recs = (const EcMultiRec*)s.d_jobs;
+  const uint64_t* d_masks = (const uint64_t*)(s.d_jobs + off_mask);
+  const int* d_base = (const int*)(s.d_jobs + off_base);
+  const int* d_act = (const int*)(s.d_jobs + off_act);
+  const long vecs = (long)(chunk_bytes >> 4);
+  const MatmulCfg c = matmul_cfg(vecs, (long)n_act);
+  // one event pair around the whole call, launches back to back
+  HIP_TRY(hipEventRecord(s.ev_start, s.stream));
+  for (int p = 0; p < n_pass; p++) {
+    const bool ok = dispatch_nout(
+        std::min(ECX_MULTI_OUT, m - p * ECX_MULTI_OUT),
+        [&](auto NO, auto NTF, auto LASTF) {
+          hipLaunchKernelGGL(
+              (ec_gf_update_kernel<NO(), NTF(), LASTF()>), c.grid, dim3(256),
+              0, s.stream, (uint8_t*)dptr, (const uint8_t*)d_new, d_recs + p,
+              d_masks, d_base, d_act, k, (long)chunk_bytes, cps, vecs);
+        },
+        c.nt, p == n_pass - 1);
+    if (!ok) return ECX_ERR_INVAL;
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
+  s.timed = true;
+  return ECX_OK;
+}
+
+int ecx_update_plan_probe(int k, int m, const uint64_t* write_masks, long n,
+                          long* new_base, int* active, int* n_active) {
+  // CPU-only: the preparation ecx_update_batch performs (same plan_update).
+  // Outputs are written only on success.
+  if (!write_masks || !new_base || !active || !n_active || n <= 0 ||
+      n > 65535 || k < 1 || m < 1 || k > ECX_MAX_K || m > ECX_MAX_K)
+    return ECX_ERR_INVAL;
+  ecx::UpdatePlan plan;
+  if (!ecx::plan_update(k, m, write_masks, n, plan)) return ECX_ERR_INVAL;
+  std::copy(plan.new_base.begin(), plan.new_base.end(), new_base);
+  std::copy(plan.active.begin(), plan.active.end(), active);
+  *n_active = (int)plan.active.size();
+  return plan.launches;
 }
 
 int ecx_set_matrix(ecx_ctx* ctx, const uint8_t* coding_rows) {
@@ -3479,6 +3651,81 @@ int ecx_apply_delta_host(ecx_ctx* ctx, const uint8_t* delta, int data_shard,
   if (r != ECX_OK) return r;
   HIP_TRY(hipMemcpyAsync(parity, s.d_stage + bytes, bytes,
                          hipMemcpyDeviceToHost, s.stream));
+  HIP_TRY(wait_stream(s.stream));
+  return ECX_OK;
+}
+
+int ecx_apply_deltas_host(ecx_ctx* ctx, const uint8_t* const* deltas,
+                          const int* data_shards, int n_in,
+                          uint8_t* const* parities, const int* coding_shards,
+                          int n_out, size_t bytes) {
+  // every (delta, parity) pair of one apply_delta call in one staged round
+  // trip: parities[j] ^= XOR_i gen[coding_shards[j]][data_shards[i]] *
+  // deltas[i] (the whole loop of ErasureCodeIsa.cc:333-366 /
+  // ErasureCodeJerasure.cc:285-331), each buffer over PCIe once
+  if (!ctx || !deltas || !data_shards || !parities || !coding_shards ||
+      n_in < 1 || n_in > ctx->k || n_out < 1 || n_out > ctx->m || bytes % 16)
+    return ECX_ERR_INVAL;
+  const int k = ctx->k;
+  for (int i = 0; i < n_in; i++)
+    if (!deltas[i] || data_shards[i] < 0 || data_shards[i] >= k)
+      return ECX_ERR_INVAL;
+  for (int j = 0; j < n_out; j++)
+    if (!parities[j] || coding_shards[j] < k || coding_shards[j] >= k + ctx->m)
+      return ECX_ERR_INVAL;
+  // refused by the bitmatrix launcher, but only after the uploads
+  if (ctx->is_bitmatrix() && bytes % ((size_t)ctx->w * ctx->pkt))
+    return ECX_ERR_INVAL;
+  if (bytes == 0) return ECX_OK;
+  const int si = (int)(ctx->rr++ % ctx->slots.size());
+  Slot& s = ctx->slots[si];
+  std::lock_guard<std::recursive_mutex> g(s.mu);
+  int r = ensure_stage(ctx, s, (size_t)(n_in + n_out) * bytes);
+  if (r != ECX_OK) return r;
+  HIP_TRY(hipSetDevice(ctx->device));
+  // one "stripe" in the stage buffer: the deltas, the parities behind them
+  int src_ids[ECX_MAX_K], out_ids[ECX_MAX_K];
+  stripe_ids(n_in, n_out, src_ids, out_ids);
+  for (int i = 0; i < n_in; i++)
+    HIP_TRY(hipMemcpyAsync(s.d_stage + (size_t)i * bytes, deltas[i], bytes,
+                           hipMemcpyHostToDevice, s.stream));
+  for (int j = 0; j < n_out; j++)
+    HIP_TRY(hipMemcpyAsync(s.d_stage + (size_t)out_ids[j] * bytes,
+                           parities[j], bytes, hipMemcpyHostToDevice,
+                           s.stream));
+  if (ctx->is_bitmatrix()) {
+    // the schedule-delta kernel takes one w x w block: per-pair launches,
+    // all inside this one staged call
+    for (int i = 0; i < n_in && r == ECX_OK; i++)
+      for (int j = 0; j < n_out && r == ECX_OK; j++)
+        r = ecx_apply_delta_dev(ctx, s.d_stage + (size_t)i * bytes,
+                                data_shards[i], coding_shards[j],
+                                s.d_stage + (size_t)out_ids[j] * bytes, bytes,
+                                si);
+  } else if (ctx->is_w16()) {
+    std::vector<uint16_t> cf((size_t)n_out * n_in);
+    for (int j = 0; j < n_out; j++)
+      for (int i = 0; i < n_in; i++)
+        cf[(size_t)j * n_in + i] =
+            ctx->gen16[(size_t)coding_shards[j] * k + data_shards[i]];
+    r = run_matmul16(ctx, si, s.d_stage, s.d_stage, src_ids, n_in, out_ids,
+                     n_out, cf.data(), 1, bytes, /*accum=*/true, false);
+  } else {
+    std::vector<uint8_t> cf((size_t)n_out * n_in);
+    for (int j = 0; j < n_out; j++)
+      for (int i = 0; i < n_in; i++)
+        cf[(size_t)j * n_in + i] =
+            ctx->gen[(size_t)coding_shards[j] * k + data_shards[i]];
+    r = run_matmul(ctx, si, s.d_stage, s.d_stage, src_ids, n_in, out_ids,
+                   n_out, cf.data(), nullptr, 1, bytes, /*accum=*/true);
+  }
+  if (r != ECX_OK) {
+    (void)hipStreamSynchronize(s.stream);  // quiesce before buffer reuse
+    return r;
+  }
+  for (int j = 0; j < n_out; j++)
+    HIP_TRY(hipMemcpyAsync(parities[j], s.d_stage + (size_t)out_ids[j] * bytes,
+                           bytes, hipMemcpyDeviceToHost, s.stream));
   HIP_TRY(wait_stream(s.stream));
   return ECX_OK;
 }

@@ -229,18 +229,28 @@ class ErasureCodeShec final : public ErasureCode {
 
   void apply_delta(const shard_id_map<buffer> &in,
                    shard_id_map<buffer> &out) override {
-    // ErasureCodeShec apply_delta (:470-505): per (data, coding) pair,
-    // coefficient from the shingled matrix (zero => no-op)
+    // ErasureCodeShec apply_delta (:470-505): the (data, coding) pairs,
+    // coefficient from the shingled matrix (zero => no-op), collected into
+    // one staged call
+    std::vector<const uint8_t *> deltas;
+    std::vector<uint8_t *> parities;
+    std::vector<int> datashards, codingshards;
+    size_t size = 0;
     for (auto &&[datashard, databuf] : in) {
       if ((int)datashard >= k_) continue;
-      for (auto &&[codingshard, codingbuf] : out) {
-        if ((int)codingshard < k_) continue;
-        ecx_apply_delta_host(ctx_, databuf.c_str(), (int)datashard,
-                             (int)codingshard,
-                             const_cast<uint8_t *>(codingbuf.c_str()),
-                             codingbuf.length());
-      }
+      deltas.push_back(databuf.c_str());
+      datashards.push_back((int)datashard);
     }
+    for (auto &&[codingshard, codingbuf] : out) {
+      if ((int)codingshard < k_) continue;
+      parities.push_back(const_cast<uint8_t *>(codingbuf.c_str()));
+      codingshards.push_back((int)codingshard);
+      size = codingbuf.length();
+    }
+    if (deltas.empty() || parities.empty()) return;
+    ecx_apply_deltas_host(ctx_, deltas.data(), datashards.data(),
+                          (int)deltas.size(), parities.data(),
+                          codingshards.data(), (int)parities.size(), size);
   }
 };
 

@@ -17,7 +17,9 @@
  *     -> ecx_encode_delta()                            ErasureCodeIsa.cc:317-328
  *   galois_w08_region_multiply accumulate /          ErasureCodeJerasure.cc:285-331,
  *     isa ec_encode_data_update (apply_delta)          ErasureCodeIsa.cc:333-366
- *     -> ecx_apply_delta()
+ *     -> ecx_apply_delta()                           (whole call fused:
+ *                                                    ecx_apply_deltas_host; over a
+ *                                                    batch: ecx_update_batch)
  *   minimum_to_decode survivor choice                src/erasure-code/ErasureCode.cc:154-170
  *     -> ecx_minimum_to_decode()
  *   get_chunk_size / get_alignment                   ErasureCodeIsa.cc:65-79,
@@ -230,6 +232,41 @@ ECX_API int ecx_decode_multi_plan_probe(int technique, int k, int m,
                                         const uint64_t *present_masks, long n,
                                         int *plan_of_stripe, int *n_plans);
 
+/* ---------------- per-stripe write sets (write batching) ------------------
+ * The partial-write counterpart of the per-stripe erasure patterns above: a
+ * shim that batches small overwrites holds stripes that each replace a
+ * DIFFERENT set of data chunks. dptr is the standard batch buffer with the
+ * old data and old parity; write_masks[s] bit j (j < k) set => data chunk j
+ * of stripe s is overwritten, 0 => the stripe is not touched at all. d_new
+ * is a device buffer of the new chunks packed, stripe ascending then chunk
+ * id ascending, chunk_bytes each: stripe s's first new chunk has index
+ * new_base[s] = sum of the popcounts of the masks before s. Per stripe, for
+ * each set bit j and each parity row r:
+ *   P_r ^= G[k+r][j] * (old_j ^ new_j), then chunk j takes its new content
+ * — encode_delta + apply_delta of every (data, coding) pair
+ * (ErasureCodeIsa.cc:333-366, ErasureCodeJerasure.cc:285-331) over the whole
+ * batch in ceil(m/4) launches whatever the masks are. Delta semantics: the
+ * parity is read and corrected, never recomputed (a parity that was
+ * inconsistent stays off by exactly the same bytes), and data chunks that
+ * did not change are not read. All validation precedes the first launch:
+ * ECX_ERR_INVAL for a NULL pointer, bad slot, chunk_bytes % 16, n_stripes
+ * outside 1..65535, a mask bit at position k or above, a bitmatrix or w=16
+ * context (as for ecx_*_slices and *_multi), or a d_new range that
+ * intersects the batch. Every mask 0: ECX_OK, nothing launched.
+ * ecx_last_kernel_ms covers the whole call (first launch to last). */
+ECX_API int ecx_update_batch(ecx_ctx *ctx, void *dptr, long n_stripes,
+                             size_t chunk_bytes, const void *d_new,
+                             const uint64_t *write_masks, int slot);
+/* CPU-only (no GPU context): the host-side preparation of the call above.
+ * new_base[n] as defined there; active[] = ascending list of the stripes
+ * with a nonzero mask (room for n), *n_active = how many. Returns the number
+ * of kernel launches (ceil(m/4), 0 if no stripe is active), or
+ * ECX_ERR_INVAL for a mask bit at position k or above (outputs are then
+ * left unwritten). */
+ECX_API int ecx_update_plan_probe(int k, int m, const uint64_t *write_masks,
+                                  long n, long *new_base, int *active,
+                                  int *n_active);
+
 /* Replace the coding rows of the generator with a custom m x k matrix
  * (clears decode-plan caches). Lets composed codecs — SHEC's shingled
  * matrix (src/erasure-code/shec/ErasureCodeShec.cc:700-768), custom
@@ -321,6 +358,20 @@ ECX_API int ecx_encode_delta_host(ecx_ctx *ctx, const uint8_t *old_data,
 ECX_API int ecx_apply_delta_host(ecx_ctx *ctx, const uint8_t *delta,
                                  int data_shard, int coding_shard,
                                  uint8_t *parity, size_t bytes);
+/* Fused form of ecx_apply_delta_host for a whole apply_delta call
+ * (ErasureCodeIsa.cc:333-366, ErasureCodeJerasure.cc:285-331): for every j,
+ *   parities[j] ^= XOR_i G[coding_shards[j]][data_shards[i]] * deltas[i]
+ * with every delta and every parity uploaded once, one accumulating launch
+ * (w=16: per <= 4 parities; bitmatrix: one per pair), every parity
+ * downloaded once and a single wait at the end. Bytes identical to looping
+ * ecx_apply_delta_host over the pairs, for every technique. ECX_ERR_INVAL
+ * for NULL pointers, shard ids out of range, n_in outside 1..k, n_out
+ * outside 1..m or bytes % 16. */
+ECX_API int ecx_apply_deltas_host(ecx_ctx *ctx, const uint8_t *const *deltas,
+                                  const int *data_shards, int n_in,
+                                  uint8_t *const *parities,
+                                  const int *coding_shards, int n_out,
+                                  size_t bytes);
 
 #ifdef __cplusplus
 }
