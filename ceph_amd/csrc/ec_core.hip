@@ -1045,7 +1045,10 @@ __global__ __launch_bounds__(256, 2) void ec_bitmatrix_pipe_kernel(
     const long sw_off = sw * (long)w * pkt + (long)win * q;
     for (int g = 0; g < G; g++) {
       int chunk = wave + g * nwaves;
-      if (chunk >= chunks) chunk -= chunks;  // wrap (duplicate, benign)
+      // wrap (duplicate, benign); modulo, since with fewer chunks than
+      // waves (64 items: one chunk) one subtraction leaves waves 2-3 past
+      // the window image
+      if (chunk >= chunks) chunk %= chunks;
       const int t0 = chunk << 6;
       const int t = t0 + lane;
       const int jc = t >> vq_shift;
