@@ -7,6 +7,7 @@
 // fallback — init() fails with -ENODEV when no GPU is visible.
 #include <cerrno>
 #include <cstring>
+#include <iostream>
 #include <memory>
 #include <ostream>
 #include <sstream>
@@ -218,9 +219,13 @@ class ErasureCodeMi355x final : public ErasureCode {
 
   void encode_delta(const buffer &old_data, const buffer &new_data,
                     buffer *delta_maybe_in_place) override {
-    ecx_encode_delta_host(ctx_, old_data.c_str(), new_data.c_str(),
-                          delta_maybe_in_place->c_str(),
-                          delta_maybe_in_place->length());
+    int r = ecx_encode_delta_host(ctx_, old_data.c_str(), new_data.c_str(),
+                                  delta_maybe_in_place->c_str(),
+                                  delta_maybe_in_place->length());
+    // void, as in the reference: a refusal leaves the delta unwritten, so
+    // at least say so
+    if (r != ECX_OK)
+      std::cerr << "mi355x: encode_delta refused (" << r << ")\n";
   }
 
   void apply_delta(const shard_id_map<buffer> &in,
@@ -245,9 +250,13 @@ class ErasureCodeMi355x final : public ErasureCode {
       size = codingbuf.length();
     }
     if (deltas.empty() || parities.empty()) return;
-    ecx_apply_deltas_host(ctx_, deltas.data(), datashards.data(),
-                          (int)deltas.size(), parities.data(),
-                          codingshards.data(), (int)parities.size(), size);
+    int r = ecx_apply_deltas_host(ctx_, deltas.data(), datashards.data(),
+                                  (int)deltas.size(), parities.data(),
+                                  codingshards.data(), (int)parities.size(),
+                                  size);
+    if (r != ECX_OK)
+      std::cerr << "mi355x: apply_delta refused (" << r
+                << "), parity left unchanged\n";
   }
 };
 

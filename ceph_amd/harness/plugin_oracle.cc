@@ -236,6 +236,21 @@ class ErasureCodeOracle final : public ErasureCode {
                                    packetsize_);
           continue;
         }
+        if (is_w16()) {
+          // GF(2^16) over little-endian u16 symbols; gen_ is not built for
+          // this technique, the coefficients live in gen16_
+          const uint16_t c16 =
+              gen16_[(size_t)(int)codingshard * k_ + (int)datashard];
+          uint8_t *cp = const_cast<uint8_t *>(codingbuf.c_str());
+          const uint8_t *dp = databuf.c_str();
+          for (size_t off = 0; off + 2 <= codingbuf.length(); off += 2) {
+            uint16_t d = (uint16_t)(dp[off] | dp[off + 1] << 8);
+            uint16_t p = ecref_gf16_mul(c16, d);
+            cp[off] ^= (uint8_t)p;
+            cp[off + 1] ^= (uint8_t)(p >> 8);
+          }
+          continue;
+        }
         uint8_t c = gen_[(size_t)(int)codingshard * k_ + (int)datashard];
         ecref_region_mul_xor(c, databuf.c_str(),
                              const_cast<uint8_t *>(codingbuf.c_str()),

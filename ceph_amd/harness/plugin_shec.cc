@@ -9,6 +9,7 @@
 // ErasureCodeShec.cc:1030-1046). No CPU fallback.
 #include <cerrno>
 #include <cstring>
+#include <iostream>
 #include <memory>
 #include <ostream>
 #include <vector>
@@ -223,8 +224,12 @@ class ErasureCodeShec final : public ErasureCode {
 
   void encode_delta(const buffer &old_data, const buffer &new_data,
                     buffer *delta) override {
-    ecx_encode_delta_host(ctx_, old_data.c_str(), new_data.c_str(),
-                          delta->c_str(), delta->length());
+    int r = ecx_encode_delta_host(ctx_, old_data.c_str(), new_data.c_str(),
+                                  delta->c_str(), delta->length());
+    // void, as in the reference: a refusal leaves the delta unwritten, so
+    // at least say so
+    if (r != ECX_OK)
+      std::cerr << "shec: encode_delta refused (" << r << ")\n";
   }
 
   void apply_delta(const shard_id_map<buffer> &in,
@@ -248,9 +253,13 @@ class ErasureCodeShec final : public ErasureCode {
       size = codingbuf.length();
     }
     if (deltas.empty() || parities.empty()) return;
-    ecx_apply_deltas_host(ctx_, deltas.data(), datashards.data(),
-                          (int)deltas.size(), parities.data(),
-                          codingshards.data(), (int)parities.size(), size);
+    int r = ecx_apply_deltas_host(ctx_, deltas.data(), datashards.data(),
+                                  (int)deltas.size(), parities.data(),
+                                  codingshards.data(), (int)parities.size(),
+                                  size);
+    if (r != ECX_OK)
+      std::cerr << "shec: apply_delta refused (" << r
+                << "), parity left unchanged\n";
   }
 };
 

@@ -181,6 +181,44 @@ int main(int argc, char **argv) {
     }
   }
   {
+    // w=16 parity delta == re-encode: GF(2^16) coefficients over
+    // little-endian u16 symbols, two data chunks overwritten at once
+    ErasureCodeProfile p{{"k", "4"}, {"m", "3"}, {"w", "16"},
+                         {"technique", "jerasure_reed_sol_van"}};
+    ErasureCodeInterfaceRef ec4;
+    int r = reg.factory("oracle", dir, p, &ec4, &ss);
+    CHECK(r == 0, "oracle jerasure_reed_sol_van w=16 factory");
+    if (r == 0) {
+      const unsigned C = ec4->get_chunk_size(4 * 1000);
+      std::mt19937_64 rng(16);
+      auto random_chunk = [&] {
+        buffer b = buffer::create_aligned(C);
+        for (size_t w = 0; w < C / 8; w++) ((uint64_t *)b.c_str())[w] = rng();
+        return b;
+      };
+      shard_id_map<buffer> in(7), out(7);
+      for (int i = 0; i < 4; i++) in[i] = random_chunk();
+      for (int j = 4; j < 7; j++) out[j] = buffer::create_aligned(C);
+      CHECK(ec4->encode_chunks(in, out) == 0, "w=16 encode");
+      shard_id_map<buffer> din(7), dout(7);
+      for (int i : {0, 3}) {
+        buffer newc = random_chunk();
+        din[i] = buffer::create_aligned(C);
+        ec4->encode_delta(in.at(i), newc, &din[i]);
+        in[i] = newc;
+      }
+      for (int j = 4; j < 7; j++) dout[j] = out.at(j);
+      ec4->apply_delta(din, dout);
+      shard_id_map<buffer> out2(7);
+      for (int j = 4; j < 7; j++) out2[j] = buffer::create_aligned(C);
+      ec4->encode_chunks(in, out2);
+      bool same = true;
+      for (int j = 4; j < 7; j++)
+        same &= !std::memcmp(out.at(j).c_str(), out2.at(j).c_str(), C);
+      CHECK(same, "w=16 parity delta == re-encode");
+    }
+  }
+  {
     // minimum_to_decode semantics (ErasureCode.cc:154-170)
     shard_id_set want, avail, minimum;
     want.insert(0);

@@ -38,8 +38,10 @@ def test_mi355x_plugin_decode_exhaustive_verifies():
 
 
 def test_mi355x_vs_oracle_plugin_same_parity(tmp_path):
-    """The GPU plugin and the oracle fixture plugin produce identical
-    parity through the same harness path (same seed => same input)."""
+    """The C ABI through ctypes (EcContext.encode_chunks, no plugin is
+    loaded) produces the parity of the Python oracle for the same input.
+    The two plugins are compared through the harness, method by method, in
+    test_gpu_plugin_diff.py."""
     import ctypes
     import numpy as np
     import ceph_amd
