@@ -110,6 +110,10 @@ def _lib():
         ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64),
         ctypes.c_long, ctypes.POINTER(ctypes.c_long),
         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    lib.ecx_bitmatrix_plan_probe.argtypes = [
+        ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_int)]
     lib.ecx_apply_deltas_host.argtypes = [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
         ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
@@ -258,6 +262,37 @@ def update_plan_probe(k, m, masks):
         act.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
         ctypes.byref(n_act)), "ecx_update_plan_probe")
     return r, base[:len(a)], act[:n_act.value]
+
+
+_BIT_KNOBS = (("ECX_BITQ", 16), ("ECX_BITW", 8), ("ECX_BITREG", 2),
+              ("ECX_BITPIPE", 0), ("ECX_BITT", 256), ("ECX_BITXCD", 0))
+
+
+def bitmatrix_plan_probe(n_src, n_out, pkt, chunk_bytes, n_ops, knobs=None,
+                         w=8):
+    """CPU-only: what the bitmatrix launcher would launch for n_out outputs
+    over n_src sources of chunk_bytes each, whose bit rows have n_ops set
+    bits. knobs maps ECX_BIT* names to values as the environment would give
+    them (missing: the default). Returns a dict: kernel ("lds", "reg" or
+    "pipe"), nr, n_pos, grid, threads, q, vq_shift and, for the two LDS
+    kernels, vqs, staging ("dma" or "reg"), items, wps, n_windows, wpb,
+    lds_bytes, xcdmap."""
+    knobs = knobs or {}
+    kn = (ctypes.c_int * 6)(*[int(knobs.get(n, d)) for n, d in _BIT_KNOBS])
+    out = (ctypes.c_int * 16)()
+    _ck(lib().ecx_bitmatrix_plan_probe(kn, w, pkt, n_src, n_out, n_ops,
+                                       chunk_bytes, out),
+        "ecx_bitmatrix_plan_probe")
+    kernel = ("lds", "reg", "pipe")[out[0]]
+    g = dict(kernel=kernel, grid=out[11], threads=out[12], q=out[3],
+             vq_shift=out[4])
+    if kernel == "reg":
+        g.update(nr=out[1], n_pos=out[2])
+    else:
+        g.update(vqs=out[5], staging="dma" if out[6] else "reg",
+                 items=out[7], wps=out[8], n_windows=out[9], wpb=out[10],
+                 lds_bytes=out[13], xcdmap=bool(out[14]))
+    return g
 
 
 def _ptr_array(bufs):

@@ -49,6 +49,7 @@
 #include "gf.h"
 #include "decode_multi.h"
 #include "update_plan.h"
+#include "bit_plan.h"
 #include "stream_walk.h"
 
 // ---------------------------------------------------------------------------
@@ -57,6 +58,13 @@
 
 #define ECX_MAX_K 32     // matches isa MAX_K (ErasureCodeIsa.h:48)
 #define ECX_MAX_OUT 8    // outputs per launch; host splits larger n_out
+
+// the bitmatrix job headers are filled by bit_plan.cpp, which cannot see
+// the two limits above
+using ecx::EcBitParams;
+using ecx::EcBitRegParams;
+static_assert(ecx::BIT_MAX_K == ECX_MAX_K && ecx::BIT_MAX_OUT == ECX_MAX_OUT,
+              "bit_plan.h restates ECX_MAX_K / ECX_MAX_OUT");
 
 // Per-launch parameter block, copied to device scratch before each launch.
 struct EcLaunchParams {
@@ -718,23 +726,71 @@ __global__ __launch_bounds__(256, 2) void ec_gf16_matmul_kernel(
 // kernel stages a q-byte window of all k*w packets in LDS once and computes
 // every output row from LDS, keeping HBM traffic algorithmic ((k+m)/k) —
 // the CDNA-native answer to jerasure's CPU XOR schedules.
-struct EcBitParams {
-  int n_src;   // k
-  int n_out;   // output chunks this launch (rows = n_out*w)
-  int w;
-  int pkt;     // packetsize bytes
-  int q;       // LDS window bytes (power-of-two divisor of pkt)
-  int vq_shift;  // log2(q/16)
-  int src_ids[ECX_MAX_K];
-  int out_ids[ECX_MAX_OUT];
-  uint16_t row_off[ECX_MAX_OUT * 8 + 1];  // prefix offsets into ops[]
-  // rows are stored sorted by op count so the 4 rows sharing a wave have
-  // similar lengths (divergence waste 5.6-7.8% -> 0.6-3.5% measured);
-  // row_map[r] = original row id (output chunk out_ids[orig/w], packet
-  // orig%w)
-  uint8_t row_map[ECX_MAX_OUT * 8];
-  // blob continues with uint16 ops[row_off[n_rows]]: values j*w+c
-};
+// EcBitParams (the job header both LDS kernels read) is in bit_plan.h.
+
+// One wave's DMA of the 64 consecutive window items from t0 into an LDS
+// image (global_load_lds_dwordx4): the image is lane-linear in the item
+// index (byte offset = t*16), exactly the wave-uniform-base + lane*16
+// layout the instruction writes. Unlike the v1 register-staged loop (1
+// outstanding load per thread -> the chip sat latency-starved: PMC
+// SQ_WAIT_ANY/WAVE 0.79, LDS 4% active), every load of the phase is in
+// flight at once and there is no ds_write pass. aux=2 (nt) on the NT path:
+// each window is read once by exactly one workgroup. Item t is 16 B vector
+// v of packet c of source j, t = ((j*w + c) << vq_shift) + v.
+template <bool NT>
+__device__ __forceinline__ void ecx_bit_glds(
+    const EcBitParams* bp, const uint8_t* sbase, long chunk_bytes,
+    long sw_off, int pkt, int w, int vq_shift, uint8_t* image, int t0,
+    int lane) {
+  const int t = t0 + lane;
+  const int jc = t >> vq_shift;
+  const int v = t - (jc << vq_shift);
+  const int j = jc / w, c = jc - j * w;
+  const uint8_t* src = sbase + (long)bp->src_ids[j] * chunk_bytes + sw_off +
+                       (long)c * pkt + (long)v * 16;
+  auto gsrc = (const __attribute__((address_space(1))) uint32_t*)src;
+  auto ldst =
+      (__attribute__((address_space(3))) uint32_t*)(image + (size_t)t0 * 16);
+  if (NT)
+    __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 0, 2);
+  else
+    __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 0, 0);
+}
+
+// The output rows of window `win` of superword `sw` from its LDS image and
+// the staged op list. Item-parallel (one 16B vec of one output row per
+// item): A/B showed this beats a row-per-wave readlane variant — with q=512
+// the row-per-wave form idles half of each wave (vq=32) and larger q
+// collapses residency; LDS op reads broadcast cheaply.
+template <bool NT, bool ACCUM>
+__device__ __forceinline__ void ecx_bit_rows(
+    const EcBitParams* bp, uint8_t* obase, long chunk_bytes, long sw, int win,
+    int pkt, int w, int q, int vq, int vq_shift, int n_rows,
+    const uint8_t* image, const uint16_t* s_ops) {
+  for (int t = threadIdx.x; t < n_rows * vq; t += blockDim.x) {
+    const int r = t >> vq_shift;
+    const int v = t - (r << vq_shift);
+    const int orig = bp->row_map[r];
+    v4u* dst = reinterpret_cast<v4u*>(
+        obase + (long)bp->out_ids[orig / w] * chunk_bytes +
+        sw * (long)w * pkt + (long)(orig % w) * pkt + (long)win * q +
+        (long)v * 16);
+    // ACCUM = parity-delta apply (schedule_apply_delta semantics,
+    // ErasureCodeJerasure.cc:348-377): XOR into the existing parity
+    v4u acc = ACCUM ? *dst : v4u{0, 0, 0, 0};
+    const int b0 = bp->row_off[r], b1 = bp->row_off[r + 1];
+    for (int o = b0; o < b1; o++) {
+      const int jc = s_ops[o];
+      const v4u d = *reinterpret_cast<const v4u*>(image + (size_t)jc * q +
+                                                  (size_t)v * 16);
+      acc.x ^= d.x; acc.y ^= d.y; acc.z ^= d.z; acc.w ^= d.w;
+    }
+    if (NT)
+      __builtin_nontemporal_store(acc, dst);
+    else
+      *dst = acc;
+  }
+}
 
 // VQS >= 0 specialises the window geometry at compile time (w = 8,
 // q = 16 << VQS): the generic form's runtime divisions/shifts and
@@ -807,35 +863,15 @@ __global__ __launch_bounds__(256, 2) void ec_bitmatrix_kernel(
     // is overwritten (first window: orders the ops staging)
     __syncthreads();
 
-    // Window staging via LDS-DMA (global_load_lds_dwordx4): the LDS
-    // image is lane-linear in the item index (byte offset = t*16),
-    // exactly the wave-uniform-base + lane*16 layout the instruction
-    // writes. Unlike the v1 register-staged loop (1 outstanding load per
-    // thread -> the chip sat latency-starved: PMC SQ_WAIT_ANY/WAVE 0.79,
-    // LDS 4% active), every load of the phase is in flight at once and
-    // there is no ds_write pass; __syncthreads() drains the DMA (its
-    // fence emits vmcnt(0) while a glds is pending). aux=2 (nt) on the
-    // NT path: each window is read once by exactly one workgroup.
+    // Window staging: ecx_bit_glds per wave-chunk; __syncthreads() drains
+    // the DMA (its fence emits vmcnt(0) while a glds is pending).
     if ((total_items & 63) == 0) {
       const int lane = threadIdx.x & 63;
       const int nwaves = blockDim.x >> 6;
       for (int t0 = (int)(threadIdx.x >> 6) * 64; t0 < total_items;
-           t0 += nwaves * 64) {
-        const int t = t0 + lane;
-        const int jc = t >> vq_shift;
-        const int v = t - (jc << vq_shift);
-        const int j = jc / w, c = jc - j * w;
-        const uint8_t* src = sbase + (long)bp->src_ids[j] * chunk_bytes +
-                             sw_off + (long)c * pkt + (long)v * 16;
-        auto gsrc = (const __attribute__((address_space(1))) uint32_t*)src;
-        auto ldst =
-            (__attribute__((address_space(3))) uint32_t*)(s_data +
-                                                          (size_t)t0 * 16);
-        if (NT)
-          __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 0, 2);
-        else
-          __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 0, 0);
-      }
+           t0 += nwaves * 64)
+        ecx_bit_glds<NT>(bp, sbase, chunk_bytes, sw_off, pkt, w, vq_shift,
+                         s_data, t0, lane);
     } else {
       // odd shapes (q < 128 with small k): register staging as in v1
       for (int t = threadIdx.x; t < total_items; t += blockDim.x) {
@@ -852,33 +888,8 @@ __global__ __launch_bounds__(256, 2) void ec_bitmatrix_kernel(
     }
     __syncthreads();
 
-    // Item-parallel compute (one 16B vec of one output row per item): A/B
-    // showed this beats a row-per-wave readlane variant — with q=512 the
-    // row-per-wave form idles half of each wave (vq=32) and larger q
-    // collapses residency; LDS op reads broadcast cheaply.
-    for (int t = threadIdx.x; t < n_rows * vq; t += blockDim.x) {
-      const int r = t >> vq_shift;
-      const int v = t - (r << vq_shift);
-      const int orig = bp->row_map[r];
-      v4u* dst = reinterpret_cast<v4u*>(
-          obase + (long)bp->out_ids[orig / w] * chunk_bytes +
-          sw * (long)w * pkt + (long)(orig % w) * pkt + (long)win * q +
-          (long)v * 16);
-      // ACCUM = parity-delta apply (schedule_apply_delta semantics,
-      // ErasureCodeJerasure.cc:348-377): XOR into the existing parity
-      v4u acc = ACCUM ? *dst : v4u{0, 0, 0, 0};
-      const int b0 = bp->row_off[r], b1 = bp->row_off[r + 1];
-      for (int o = b0; o < b1; o++) {
-        const int jc = s_ops[o];
-        const v4u d = *reinterpret_cast<const v4u*>(
-            s_data + (size_t)jc * q + (size_t)v * 16);
-        acc.x ^= d.x; acc.y ^= d.y; acc.z ^= d.z; acc.w ^= d.w;
-      }
-      if (NT)
-        __builtin_nontemporal_store(acc, dst);
-      else
-        *dst = acc;
-    }
+    ecx_bit_rows<NT, ACCUM>(bp, obase, chunk_bytes, sw, win, pkt, w, q, vq,
+                            vq_shift, n_rows, s_data, s_ops);
   }
 }
 
@@ -893,14 +904,7 @@ __global__ __launch_bounds__(256, 2) void ec_bitmatrix_kernel(
 // sustains 5.97 at the same 2.67:1 R/W mix — the mix is not the
 // ceiling, the burst structure is (membench ladder + bench r2).
 // NR <= 32 (n_out <= 4); larger n_out falls back to the LDS kernel.
-struct EcBitRegParams {
-  int n_src;
-  int pkt;
-  int src_ids[ECX_MAX_K];
-  int out_ids[4];
-  uint32_t colmask[ECX_MAX_K * 8];  // bit r of colmask[j*8+c]: row r uses (j,c)
-};
-
+// Job header: EcBitRegParams (bit_plan.h).
 template <bool NT, bool ACCUM, int NR>
 __global__ __launch_bounds__(256, 2) void ec_bitmatrix_reg_kernel(
     const uint8_t* __restrict__ buf, uint8_t* __restrict__ obuf,
@@ -1049,21 +1053,8 @@ __global__ __launch_bounds__(256, 2) void ec_bitmatrix_pipe_kernel(
       // waves (64 items: one chunk) one subtraction leaves waves 2-3 past
       // the window image
       if (chunk >= chunks) chunk %= chunks;
-      const int t0 = chunk << 6;
-      const int t = t0 + lane;
-      const int jc = t >> vq_shift;
-      const int v = t - (jc << vq_shift);
-      const int j = jc / w, c = jc - j * w;
-      const uint8_t* src = sbase + (long)bp->src_ids[j] * chunk_bytes +
-                           sw_off + (long)c * pkt + (long)v * 16;
-      auto gsrc = (const __attribute__((address_space(1))) uint32_t*)src;
-      auto ldst = (__attribute__((address_space(3))) uint32_t*)(dstbuf +
-                                                               (size_t)t0 *
-                                                                   16);
-      if (NT)
-        __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 0, 2);
-      else
-        __builtin_amdgcn_global_load_lds(gsrc, ldst, 16, 0, 0);
+      ecx_bit_glds<NT>(bp, sbase, chunk_bytes, sw_off, pkt, w, vq_shift,
+                       dstbuf, chunk << 6, lane);
     }
   };
 
@@ -1080,27 +1071,8 @@ __global__ __launch_bounds__(256, 2) void ec_bitmatrix_pipe_kernel(
 
     const int win = (int)(wt % windows_per_sw);
     const long sw = wt / windows_per_sw;
-    for (int t = threadIdx.x; t < n_rows * vq; t += blockDim.x) {
-      const int r = t >> vq_shift;
-      const int v = t - (r << vq_shift);
-      const int orig = bp->row_map[r];
-      v4u* dst = reinterpret_cast<v4u*>(
-          obase + (long)bp->out_ids[orig / w] * chunk_bytes +
-          sw * (long)w * pkt + (long)(orig % w) * pkt + (long)win * q +
-          (long)v * 16);
-      v4u acc = ACCUM ? *dst : v4u{0, 0, 0, 0};
-      const int b0 = bp->row_off[r], b1 = bp->row_off[r + 1];
-      for (int o = b0; o < b1; o++) {
-        const int jc = s_ops[o];
-        const v4u d = *reinterpret_cast<const v4u*>(
-            cur + (size_t)jc * q + (size_t)v * 16);
-        acc.x ^= d.x; acc.y ^= d.y; acc.z ^= d.z; acc.w ^= d.w;
-      }
-      if (NT)
-        __builtin_nontemporal_store(acc, dst);
-      else
-        *dst = acc;
-    }
+    ecx_bit_rows<NT, ACCUM>(bp, obase, chunk_bytes, sw, win, pkt, w, q, vq,
+                            vq_shift, n_rows, cur, s_ops);
     ecx_raw_barrier();  // all reads of `cur` done before wt+2 overwrites it
   }
 }
@@ -1685,6 +1657,18 @@ static int upload_params(Slot& s, const EcLaunchParams& params) {
   return ECX_OK;
 }
 
+// The event pair ecx_last_kernel_ms reads, around the launches between the
+// two calls; `on` = this launch is the one the caller wants timed.
+static hipError_t timer_start(Slot& s, bool on = true) {
+  return on ? hipEventRecord(s.ev_start, s.stream) : hipSuccess;
+}
+static hipError_t timer_stop(Slot& s, bool on = true) {
+  if (!on) return hipSuccess;
+  const hipError_t e = hipEventRecord(s.ev_stop, s.stream);
+  if (e == hipSuccess) s.timed = true;
+  return e;
+}
+
 // Launch the matmul kernel for one output group (n_out <= 4).
 static int launch_matmul(ecx_ctx* ctx, Slot& s, const uint8_t* d_buf,
                          uint8_t* d_obuf, const EcLaunchParams& params,
@@ -1697,14 +1681,11 @@ static int launch_matmul(ecx_ctx* ctx, Slot& s, const uint8_t* d_buf,
   if (r != ECX_OK) return r;
 
   const MatmulCfg c = matmul_cfg((long)(chunk_bytes >> 4), n_stripes);
-  if (time_it) HIP_TRY(hipEventRecord(s.ev_start, s.stream));
+  HIP_TRY(timer_start(s, time_it));
   r = matmul_dispatch(s.stream, d_buf, d_obuf, s.d_params, params.n_out,
                       accum, c, chunk_bytes, ctx->k + ctx->m);
   if (r != ECX_OK) return r;
-  if (time_it) {
-    HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
-    s.timed = true;
-  }
+  HIP_TRY(timer_stop(s, time_it));
   return ECX_OK;
 }
 
@@ -1849,16 +1830,13 @@ static int launch_stream(ecx_ctx* ctx, Slot& s, const uint8_t* d_buf,
                     (uint32_t)width, env_stream_xcd() == 1, grid);
   const uint64_t stripe_bytes = (uint64_t)(ctx->k + ctx->m) * chunk_bytes;
 
-  if (time_it) HIP_TRY(hipEventRecord(s.ev_start, s.stream));
+  HIP_TRY(timer_start(s, time_it));
   dispatch_nout(n_out, [&](auto NO) {
     hipLaunchKernelGGL((ec_gf_stream_kernel<NO()>), dim3(grid), dim3(256), 0,
                        s.stream, d_buf, d_obuf, p, stripe_bytes, vecs, walk);
   });
   HIP_TRY(hipGetLastError());
-  if (time_it) {
-    HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
-    s.timed = true;
-  }
+  HIP_TRY(timer_stop(s, time_it));
   return ECX_OK;
 }
 
@@ -1914,6 +1892,23 @@ static int ensure_jobs(ecx_ctx* ctx, Slot& s, size_t bytes) {
   return ECX_OK;
 }
 
+// The slot's job blob is a ring of one. open_jobs: room for `bytes`, and the
+// previous upload has left the pinned copy — s.h_jobs may be written.
+// send_jobs: s.h_jobs[0, bytes) to s.d_jobs on the slot's stream.
+static int open_jobs(ecx_ctx* ctx, Slot& s, size_t bytes) {
+  int r = ensure_jobs(ctx, s, bytes);
+  if (r != ECX_OK) return r;
+  HIP_TRY(wait_event(s.ev_jobs));
+  return ECX_OK;
+}
+
+static int send_jobs(Slot& s, size_t bytes) {
+  HIP_TRY(hipMemcpyAsync(s.d_jobs, s.h_jobs, bytes, hipMemcpyHostToDevice,
+                         s.stream));
+  HIP_TRY(hipEventRecord(s.ev_jobs, s.stream));
+  return ECX_OK;
+}
+
 static const int SLICE_VPB = 256 * 4;  // vectors per block, slice kernels
 
 static long slice_blocks(size_t bytes) {
@@ -1951,9 +1946,8 @@ static int build_slice_jobs(ecx_ctx* ctx, Slot& s, size_t head,
   const size_t off_bsl = off_voff + (size_t)n_blocks * 8;
   const size_t off_brec = off_bsl + (size_t)n_blocks * 4;
   const size_t blob = off_brec + (recs ? (size_t)n_blocks * 4 : 0);
-  int r = ensure_jobs(ctx, s, blob);
+  int r = open_jobs(ctx, s, blob);
   if (r != ECX_OK) return r;
-  HIP_TRY(wait_event(s.ev_jobs));
 
   uint64_t* ptrs = (uint64_t*)(s.h_jobs + head);
   long* svecs = (long*)(s.h_jobs + off_vecs);
@@ -2004,9 +1998,8 @@ static int run_slices(ecx_ctx* ctx, int slot_i, void* const* d_chunks,
   int r = build_slice_jobs(ctx, s, 0, d_chunks, bytes, n_slices, nullptr,
                            nullptr, (size_t)n_slices, &jt);
   if (r != ECX_OK) return r;
-  HIP_TRY(hipMemcpyAsync(s.d_jobs, s.h_jobs, jt.bytes, hipMemcpyHostToDevice,
-                         s.stream));
-  HIP_TRY(hipEventRecord(s.ev_jobs, s.stream));
+  r = send_jobs(s, jt.bytes);
+  if (r != ECX_OK) return r;
 
   for (int j0 = 0; j0 < n_out; j0 += 4) {
     int nj = std::min(4, n_out - j0);
@@ -2030,227 +2023,88 @@ static int run_slices(ecx_ctx* ctx, int slot_i, void* const* d_chunks,
   return ECX_OK;
 }
 
+// The ECX_BIT* knobs that bit_plan() acts on (bit_plan.h), as given.
+static const ecx::BitKnobs& env_bit_knobs() {
+  static const ecx::BitKnobs kn = {
+      env_int("ECX_BITQ", 16),   env_int("ECX_BITW", 8),
+      env_int("ECX_BITREG", 2),  env_int("ECX_BITPIPE", 0),
+      env_int("ECX_BITT", 256),  env_int("ECX_BITXCD", 0)};
+  return kn;
+}
+
 // Launch the bitmatrix kernel for <= ECX_MAX_OUT output chunks whose bit
-// rows (n_out*w x n_src*w) are given over the source chunk ids.
+// rows (n_out*w x n_src*w) are given over the source chunk ids. Which
+// kernel, window, grid and LDS size: bit_plan().
 static int run_bitmatrix(ecx_ctx* ctx, int slot_i, const uint8_t* d_buf,
                          uint8_t* d_obuf, const int* src_ids, int n_src,
                          const int* out_ids, int n_out,
                          const uint8_t* bit_rows, long n_stripes,
                          size_t chunk_bytes, bool time_it,
                          bool accum = false) {
-  const int w = ctx->w, pkt = ctx->pkt;
-  if (n_src < 1 || n_src > 16 || n_out < 1 || n_out > ECX_MAX_OUT)
+  const int w = ctx->w, pkt = ctx->pkt, cps = ctx->k + ctx->m;
+  // bit_rows is only as large as an admissible n_src x n_out makes it
+  if (n_src < 1 || n_src > ecx::BIT_MAX_SRC || n_out < 1 ||
+      n_out > ECX_MAX_OUT || n_stripes <= 0 || n_stripes > 65535)
     return ECX_ERR_INVAL;
-  if (chunk_bytes == 0 || chunk_bytes % ((size_t)w * pkt) || n_stripes <= 0 ||
-      n_stripes > 65535)
-    return ECX_ERR_INVAL;
+  const size_t n_ops = ecx::bit_count_ops(bit_rows, w, n_src, n_out);
+  ecx::BitPlan p;
+  int r = ecx::bit_plan(env_bit_knobs(), w, pkt, n_src, n_out, n_ops,
+                        chunk_bytes, &p);
+  if (r != ECX_OK) return r;
   Slot& s = ctx->slots[slot_i];
   std::lock_guard<std::recursive_mutex> g(s.mu);
   HIP_TRY(hipSetDevice(ctx->device));
 
-  // LDS window: largest power-of-two divisor of pkt within the LDS budget
-  // (ECX_BITQ KB). Default 16 from the MI355X sweep: small windows keep
-  // 8+ blocks/CU resident and beat large windows by ~19%
-  // (profiles/rocprof_r01_summary.md).
-  static const size_t lds_budget = [] {
-    const char* v = getenv("ECX_BITQ");
-    long kb = v ? atol(v) : 16;
-    if (kb < 8) kb = 8;
-    if (kb > 120) kb = 120;
-    return (size_t)kb * 1024;
-  }();
-  int q = 16;
-  while (q * 2 <= pkt && pkt % (q * 2) == 0 &&
-         (size_t)n_src * w * q * 2 <= lds_budget)
-    q *= 2;
-  int vq_shift = 0;
-  while ((1 << vq_shift) < q / 16) vq_shift++;
-  if ((16 << vq_shift) != q) return ECX_ERR_INVAL;
-
-  // v3 register-accumulator path (no LDS staging, no barrier): measured
-  // policy — at n_out == 1 (single-erasure decode, delta apply) the LDS
-  // kernel idles most of each block's compute items while v3 keeps every
-  // lane busy (7.13 vs 7.64 ms); at n_out >= 2 the LDS kernel wins
-  // (n_out=2 decode 8.02 vs 11.04; m=3 encode 10.43 vs 10.85).
-  // ECX_BITREG: 0 = never, 1 = always (n_out <= 4), 2/unset = auto.
-  static const int env_reg = [] {
-    const char* v = getenv("ECX_BITREG");
-    return v ? atoi(v) : 2;
-  }();
-  const bool use_reg =
-      env_reg == 1 ? n_out <= 4 : (env_reg == 2 ? n_out == 1 : false);
-  if (use_reg && w == 8 && (pkt & 15) == 0) {
-    EcBitRegParams hdr;
-    std::memset(&hdr, 0, sizeof(hdr));
-    hdr.n_src = n_src;
-    hdr.pkt = pkt;
-    for (int i = 0; i < n_src; i++) hdr.src_ids[i] = src_ids[i];
-    for (int j = 0; j < n_out; j++) hdr.out_ids[j] = out_ids[j];
-    const int W8 = n_src * 8, nr = n_out * 8;
-    for (int j = 0; j < n_src; j++)
-      for (int c = 0; c < 8; c++) {
-        uint32_t mbits = 0;
-        for (int r = 0; r < nr; r++)
-          if (bit_rows[(size_t)r * W8 + j * 8 + c]) mbits |= 1u << r;
-        hdr.colmask[j * 8 + c] = mbits;
-      }
-    int r = ensure_jobs(ctx, s, sizeof(hdr));
-    if (r != ECX_OK) return r;
-    HIP_TRY(wait_event(s.ev_jobs));
-    std::memcpy(s.h_jobs, &hdr, sizeof(hdr));
-    HIP_TRY(hipMemcpyAsync(s.d_jobs, s.h_jobs, sizeof(hdr),
-                           hipMemcpyHostToDevice, s.stream));
-    HIP_TRY(hipEventRecord(s.ev_jobs, s.stream));
-    const long n_pos = (long)(chunk_bytes >> 7);  // 16B vecs, 8 pkts/sw
-    dim3 grid((unsigned)std::min<long>((n_pos + 255) / 256, 16384),
-              (unsigned)n_stripes);
-    if (time_it) HIP_TRY(hipEventRecord(s.ev_start, s.stream));
-#define ECX_BRK(NR_)                                                    \
-  hipLaunchKernelGGL(                                                   \
-      (env_nt() ? (accum ? ec_bitmatrix_reg_kernel<true, true, NR_>       \
-                       : ec_bitmatrix_reg_kernel<true, false, NR_>)     \
-              : (accum ? ec_bitmatrix_reg_kernel<false, true, NR_>      \
-                       : ec_bitmatrix_reg_kernel<false, false, NR_>)),  \
-      grid, dim3(256), 0, s.stream, d_buf, d_obuf, s.d_jobs,            \
-      (long)chunk_bytes, ctx->k + ctx->m, n_pos)
-    switch (n_out) {
-      case 1: ECX_BRK(8); break;
-      case 2: ECX_BRK(16); break;
-      case 3: ECX_BRK(24); break;
-      default: ECX_BRK(32); break;
-    }
-#undef ECX_BRK
-    HIP_TRY(hipGetLastError());
-    if (time_it) {
-      HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
-      s.timed = true;
-    }
-    return ECX_OK;
-  }
-
-  // build blob: header + ops
-  const int n_rows = n_out * w, W = n_src * w;
-  EcBitParams hdr;
-  std::memset(&hdr, 0, sizeof(hdr));
-  hdr.n_src = n_src;
-  hdr.n_out = n_out;
-  hdr.w = w;
-  hdr.pkt = pkt;
-  hdr.q = q;
-  hdr.vq_shift = vq_shift;
-  for (int i = 0; i < n_src; i++) hdr.src_ids[i] = src_ids[i];
-  for (int j = 0; j < n_out; j++) hdr.out_ids[j] = out_ids[j];
-  std::vector<uint16_t> ops;
-  ops.reserve((size_t)n_rows * W / 2);
-  // sort rows by op count (waves span several rows; uniform lengths kill
-  // the max-over-rows divergence in the compute loop)
-  std::vector<std::pair<int, int>> order(n_rows);
-  for (int r = 0; r < n_rows; r++) {
-    int cnt = 0;
-    const uint8_t* row = bit_rows + (size_t)r * W;
-    for (int c = 0; c < W; c++) cnt += row[c] != 0;
-    order[r] = {cnt, r};
-  }
-  std::sort(order.begin(), order.end());
-  for (int rr = 0; rr < n_rows; rr++) {
-    const int r = order[rr].second;
-    hdr.row_map[rr] = (uint8_t)r;
-    hdr.row_off[rr] = (uint16_t)ops.size();
-    const uint8_t* row = bit_rows + (size_t)r * W;
-    for (int c = 0; c < W; c++)
-      if (row[c]) ops.push_back((uint16_t)c);
-  }
-  hdr.row_off[n_rows] = (uint16_t)ops.size();
-  if (ops.size() > 0xffff) return ECX_ERR_INVAL;
-  if (ops.size() & 1) ops.push_back(0);  // pad: kernel copies ops as dwords
-  size_t blob = sizeof(EcBitParams) + ops.size() * 2;
-  int r = ensure_jobs(ctx, s, blob);
+  const bool reg = p.kernel == ecx::BIT_REG;
+  const size_t blob =
+      reg ? sizeof(EcBitRegParams) : ecx::bit_lds_blob_bytes(n_ops);
+  r = open_jobs(ctx, s, blob);
   if (r != ECX_OK) return r;
-  HIP_TRY(wait_event(s.ev_jobs));
-  std::memcpy(s.h_jobs, &hdr, sizeof(hdr));
-  std::memcpy(s.h_jobs + sizeof(hdr), ops.data(), ops.size() * 2);
-  HIP_TRY(hipMemcpyAsync(s.d_jobs, s.h_jobs, blob, hipMemcpyHostToDevice,
-                         s.stream));
-  HIP_TRY(hipEventRecord(s.ev_jobs, s.stream));
+  if (reg)
+    ecx::bit_fill_reg_blob(pkt, src_ids, n_src, out_ids, n_out, bit_rows,
+                           (EcBitRegParams*)s.h_jobs);
+  else
+    ecx::bit_fill_lds_blob(p, w, pkt, src_ids, n_src, out_ids, n_out,
+                           bit_rows, s.h_jobs);
+  r = send_jobs(s, blob);
+  if (r != ECX_OK) return r;
 
-  const long sw_per_chunk = (long)(chunk_bytes / ((size_t)w * pkt));
-  const int windows_per_sw = pkt / q;
-  const long n_windows = sw_per_chunk * windows_per_sw;
-  // windows per block: amortizes the ops staging and block start/drain
-  // over several LDS-window rounds without growing the LDS footprint
-  // (q stays small => 8 blocks/CU residency); MI355X sweep default 8.
-  static const int env_wpb = [] {
-    const char* v = getenv("ECX_BITW");
-    long n = v ? atol(v) : 8;
-    if (n < 1) n = 1;
-    if (n > 4096) n = 4096;
-    return (int)n;
-  }();
-  const int wpb = env_wpb;
-  static const int env_pipe = [] {
-    // 2-buffer glds pipeline: measured SLOWER (18.0 vs 10.9 ms at wpb=8,
-    // profiles r2) — halved residency outweighs the in-block overlap at
-    // 8-blocks/CU occupancy, as the CDNA guide's regime note predicts.
-    // Kept behind the knob as a recorded negative.
-    const char* v = getenv("ECX_BITPIPE");
-    return v ? atoi(v) : 0;
-  }();
-  static const int env_bt = [] {
-    // block size: 128-thread blocks double the independent blocks per CU
-    // (16 at q=128) so co-resident blocks interleave DMA-wait and
-    // compute phases more finely
-    const char* v = getenv("ECX_BITT");
-    int n = v ? atoi(v) : 256;
-    return (n == 64 || n == 128 || n == 256) ? n : 256;
-  }();
-  static const int env_stagger = [] {
-    const char* v = getenv("ECX_BITSTAGGER");
-    return v ? atoi(v) : 0;
-  }();
-  static const int env_xcd = [] {
-    const char* v = getenv("ECX_BITXCD");
-    return v ? atoi(v) : 0;
-  }();
-  dim3 grid((unsigned)((n_windows + wpb - 1) / wpb), (unsigned)n_stripes);
-  const size_t data_bytes = (size_t)n_src * w * q;
-  const size_t ops_bytes = (ops.size() * 2 + 15) & ~15ull;
-  const int total_items = n_src * w * (q >> 4);
-  const bool pipe = env_pipe && wpb > 1 && (total_items & 63) == 0 &&
-                    2 * data_bytes + ops_bytes <= 160 * 1024;
-  size_t lds = (pipe ? 2 * data_bytes : data_bytes) + ops_bytes;
-  if (time_it) HIP_TRY(hipEventRecord(s.ev_start, s.stream));
-  if (pipe) {
-    auto kfn = env_nt() ? (accum ? ec_bitmatrix_pipe_kernel<true, true>
-                               : ec_bitmatrix_pipe_kernel<true, false>)
-                      : (accum ? ec_bitmatrix_pipe_kernel<false, true>
-                               : ec_bitmatrix_pipe_kernel<false, false>);
-    hipLaunchKernelGGL(kfn, grid, dim3(256), lds, s.stream, d_buf, d_obuf,
-                       s.d_jobs, (long)chunk_bytes, ctx->k + ctx->m,
-                       windows_per_sw, wpb, n_windows);
-  } else {
-    const long n_blocks = (n_windows + wpb - 1) / wpb;
-    const int xcdmap =
-        env_xcd && windows_per_sw == 8 && n_windows % ((long)wpb * 64) == 0 &&
-        n_blocks % 64 == 0;
-#define ECX_BMK(VQS_)                                                \
-  (env_nt() ? (accum ? ec_bitmatrix_kernel<true, true, VQS_>           \
-                   : ec_bitmatrix_kernel<true, false, VQS_>)         \
-          : (accum ? ec_bitmatrix_kernel<false, true, VQS_>          \
-                   : ec_bitmatrix_kernel<false, false, VQS_>))
-    auto kfn = ECX_BMK(-1);
-    if (w == 8 && vq_shift == 3) kfn = ECX_BMK(3);
-    if (w == 8 && vq_shift == 4) kfn = ECX_BMK(4);
-    if (w == 8 && vq_shift == 5) kfn = ECX_BMK(5);
-#undef ECX_BMK
-    hipLaunchKernelGGL(kfn, grid, dim3(env_bt), lds, s.stream, d_buf,
-                       d_obuf, s.d_jobs, (long)chunk_bytes, ctx->k + ctx->m,
-                       windows_per_sw, wpb, n_windows, env_stagger, xcdmap);
-  }
+  static const int stagger = env_int("ECX_BITSTAGGER", 0);
+  const dim3 grid((unsigned)p.grid_x, (unsigned)n_stripes);
+  HIP_TRY(timer_start(s, time_it));
+  dispatch_flags(
+      [&](auto NTF, auto AC) {
+        constexpr bool NT = decltype(NTF)::value, A = decltype(AC)::value;
+        auto lds = [&](auto VQS) {
+          hipLaunchKernelGGL(
+              (ec_bitmatrix_kernel<NT, A, decltype(VQS)::value>), grid,
+              dim3(p.threads), p.lds_bytes, s.stream, d_buf, d_obuf, s.d_jobs,
+              (long)chunk_bytes, cps, p.windows_per_sw, p.wpb, p.n_windows,
+              stagger, p.xcdmap);
+        };
+        if (reg)
+          dispatch_nout(n_out, [&](auto NO) {
+            hipLaunchKernelGGL(
+                (ec_bitmatrix_reg_kernel<NT, A, 8 * decltype(NO)::value>),
+                grid, dim3(256), 0, s.stream, d_buf, d_obuf, s.d_jobs,
+                (long)chunk_bytes, cps, p.n_pos);
+          });
+        else if (p.kernel == ecx::BIT_PIPE)
+          hipLaunchKernelGGL((ec_bitmatrix_pipe_kernel<NT, A>), grid,
+                             dim3(256), p.lds_bytes, s.stream, d_buf, d_obuf,
+                             s.d_jobs, (long)chunk_bytes, cps,
+                             p.windows_per_sw, p.wpb, p.n_windows);
+        else
+          switch (p.vqs) {
+            case 3: lds(std::integral_constant<int, 3>{}); break;
+            case 4: lds(std::integral_constant<int, 4>{}); break;
+            case 5: lds(std::integral_constant<int, 5>{}); break;
+            default: lds(std::integral_constant<int, -1>{}); break;
+          }
+      },
+      env_nt(), accum);
   HIP_TRY(hipGetLastError());
-  if (time_it) {
-    HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
-    s.timed = true;
-  }
+  HIP_TRY(timer_stop(s, time_it));
   return ECX_OK;
 }
 
@@ -2325,14 +2179,12 @@ static int run_matmul16(ecx_ctx* ctx, int slot_i, const uint8_t* d_buf,
         if (cls == 2) build_tabs16(f, c, &p.tabs[(j * n_src + i) * 20]);
       }
     size_t blob = sizeof(EcLaunch16);
-    int r = ensure_jobs(ctx, s, blob);
+    int r = open_jobs(ctx, s, blob);
     if (r != ECX_OK) return r;
-    HIP_TRY(wait_event(s.ev_jobs));
     std::memcpy(s.h_jobs, &p, blob);
-    HIP_TRY(hipMemcpyAsync(s.d_jobs, s.h_jobs, blob, hipMemcpyHostToDevice,
-                           s.stream));
-    HIP_TRY(hipEventRecord(s.ev_jobs, s.stream));
-    if (j0 == 0 && time_all) HIP_TRY(hipEventRecord(s.ev_start, s.stream));
+    r = send_jobs(s, blob);
+    if (r != ECX_OK) return r;
+    HIP_TRY(timer_start(s, j0 == 0 && time_all));
     dispatch_nout(
         nj,
         [&](auto NO, auto AC, auto NTF) {
@@ -2342,10 +2194,7 @@ static int run_matmul16(ecx_ctx* ctx, int slot_i, const uint8_t* d_buf,
         },
         accum, env_nt());
     HIP_TRY(hipGetLastError());
-    if (time_all) {
-      HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
-      s.timed = true;
-    }
+    HIP_TRY(timer_stop(s, time_all));
   }
   return ECX_OK;
 }
@@ -2598,9 +2447,8 @@ int ecx_decode_batch_multi(ecx_ctx* ctx, void* dptr, long n_stripes,
   const size_t off_pos = n_recs * sizeof(EcMultiRec);
   const size_t off_list = off_pos + (size_t)n_stripes * 4;
   const size_t blob = off_list + n_listed * 4;
-  r = ensure_jobs(ctx, s, blob);
+  r = open_jobs(ctx, s, blob);
   if (r != ECX_OK) return r;
-  HIP_TRY(wait_event(s.ev_jobs));
   multi_fill_recs((EcMultiRec*)s.h_jobs, grp, plans, ctx->k);
   std::memcpy(s.h_jobs + off_pos, grp.plan_of_stripe.data(),
               (size_t)n_stripes * 4);
@@ -2611,9 +2459,8 @@ int ecx_decode_batch_multi(ecx_ctx* ctx, void* dptr, long n_stripes,
       list += l.members.size();
     }
   }
-  HIP_TRY(hipMemcpyAsync(s.d_jobs, s.h_jobs, blob, hipMemcpyHostToDevice,
-                         s.stream));
-  HIP_TRY(hipEventRecord(s.ev_jobs, s.stream));
+  r = send_jobs(s, blob);
+  if (r != ECX_OK) return r;
 
   uint8_t* buf = (uint8_t*)dptr;
   const EcMultiRec* d_recs = (const EcMultiRec*)s.d_jobs;
@@ -2621,7 +2468,7 @@ int ecx_decode_batch_multi(ecx_ctx* ctx, void* dptr, long n_stripes,
   const int* d_list = (const int*)(s.d_jobs + off_list);
   const long vecs = (long)(chunk_bytes >> 4);
   // one event pair around the whole call, launches back to back
-  HIP_TRY(hipEventRecord(s.ev_start, s.stream));
+  HIP_TRY(timer_start(s));
   for (const auto& l : grp.launches) {
     const MatmulCfg c = matmul_cfg(vecs, (long)l.members.size());
     const bool ok = dispatch_nout(
@@ -2637,8 +2484,7 @@ int ecx_decode_batch_multi(ecx_ctx* ctx, void* dptr, long n_stripes,
     HIP_TRY(hipGetLastError());
     d_list += l.members.size();
   }
-  HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
-  s.timed = true;
+  HIP_TRY(timer_stop(s));
   return ECX_OK;
 }
 
@@ -2684,11 +2530,10 @@ int ecx_decode_slices_multi(ecx_ctx* ctx, void* const* d_chunks,
                        &jt);
   if (r != ECX_OK) return r;
   multi_fill_recs((EcMultiRec*)s.h_jobs, grp, plans, k);
-  HIP_TRY(hipMemcpyAsync(s.d_jobs, s.h_jobs, jt.bytes, hipMemcpyHostToDevice,
-                         s.stream));
-  HIP_TRY(hipEventRecord(s.ev_jobs, s.stream));
+  r = send_jobs(s, jt.bytes);
+  if (r != ECX_OK) return r;
 
-  HIP_TRY(hipEventRecord(s.ev_start, s.stream));
+  HIP_TRY(timer_start(s));
   long b0 = 0;
   for (const auto& l : grp.launches) {
     long nb = 0;
@@ -2707,8 +2552,7 @@ int ecx_decode_slices_multi(ecx_ctx* ctx, void* const* d_chunks,
     HIP_TRY(hipGetLastError());
     b0 += nb;
   }
-  HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
-  s.timed = true;
+  HIP_TRY(timer_stop(s));
   return ECX_OK;
 }
 
@@ -2770,9 +2614,8 @@ int ecx_update_batch(ecx_ctx* ctx, void* dptr, long n_stripes,
   const size_t off_base = off_mask + (size_t)n_stripes * 8;
   const size_t off_act = off_base + (size_t)n_stripes * 4;
   const size_t blob = off_act + n_act * 4;
-  int r = ensure_jobs(ctx, s, blob);
+  int r = open_jobs(ctx, s, blob);
   if (r != ECX_OK) return r;
-  HIP_TRY(wait_event(s.ev_jobs));
   {
     EcMultiRec* recs = (EcMultiRec*)s.h_jobs;
     std::memset(recs, 0, off_mask);
@@ -2788,9 +2631,8 @@ int ecx_update_batch(ecx_ctx* ctx, void* dptr, long n_stripes,
   std::memcpy(s.h_jobs + off_base, plan.new_base.data(),
               (size_t)n_stripes * 4);
   std::memcpy(s.h_jobs + off_act, plan.active.data(), n_act * 4);
-  HIP_TRY(hipMemcpyAsync(s.d_jobs, s.h_jobs, blob, hipMemcpyHostToDevice,
-                         s.stream));
-  HIP_TRY(hipEventRecord(s.ev_jobs, s.stream));
+  r = send_jobs(s, blob);
+  if (r != ECX_OK) return r;
 
   const EcMultiRec* d_recs = (const EcMultiRec*)s.d_jobs;
   const uint64_t* d_masks = (const uint64_t*)(s.d_jobs + off_mask);
@@ -2799,7 +2641,7 @@ int ecx_update_batch(ecx_ctx* ctx, void* dptr, long n_stripes,
   const long vecs = (long)(chunk_bytes >> 4);
   const MatmulCfg c = matmul_cfg(vecs, (long)n_act);
   // one event pair around the whole call, launches back to back
-  HIP_TRY(hipEventRecord(s.ev_start, s.stream));
+  HIP_TRY(timer_start(s));
   for (int p = 0; p < n_pass; p++) {
     const bool ok = dispatch_nout(
         std::min(ECX_MULTI_OUT, m - p * ECX_MULTI_OUT),
@@ -2813,8 +2655,7 @@ int ecx_update_batch(ecx_ctx* ctx, void* dptr, long n_stripes,
     if (!ok) return ECX_ERR_INVAL;
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipEventRecord(s.ev_stop, s.stream));
-  s.timed = true;
+  HIP_TRY(timer_stop(s));
   return ECX_OK;
 }
 
@@ -2831,6 +2672,25 @@ int ecx_update_plan_probe(int k, int m, const uint64_t* write_masks, long n,
   std::copy(plan.active.begin(), plan.active.end(), active);
   *n_active = (int)plan.active.size();
   return plan.launches;
+}
+
+int ecx_bitmatrix_plan_probe(const int knobs[6], int w, int pkt, int n_src,
+                             int n_out, long n_ops, size_t chunk_bytes,
+                             int out[16]) {
+  // CPU-only: the plan run_bitmatrix launches by (same bit_plan). out is
+  // written only on success; every figure of an admitted chunk fits an int.
+  if (!knobs || !out || n_ops < 0 || chunk_bytes >> 35) return ECX_ERR_INVAL;
+  const ecx::BitKnobs kn = {knobs[0], knobs[1], knobs[2],
+                            knobs[3], knobs[4], knobs[5]};
+  ecx::BitPlan p;
+  int r = ecx::bit_plan(kn, w, pkt, n_src, n_out, (size_t)n_ops, chunk_bytes,
+                        &p);
+  if (r != ECX_OK) return r;
+  const long f[16] = {p.kernel, p.nr, p.n_pos, p.q, p.vq_shift, p.vqs, p.dma,
+                      p.items, p.windows_per_sw, p.n_windows, p.wpb, p.grid_x,
+                      p.threads, (long)p.lds_bytes, p.xcdmap, 0};
+  for (int i = 0; i < 16; i++) out[i] = (int)f[i];
+  return ECX_OK;
 }
 
 int ecx_set_matrix(ecx_ctx* ctx, const uint8_t* coding_rows) {

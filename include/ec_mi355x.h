@@ -267,6 +267,28 @@ ECX_API int ecx_update_plan_probe(int k, int m, const uint64_t *write_masks,
                                   long n, long *new_base, int *active,
                                   int *n_active);
 
+/* CPU-only (no GPU context): what the bitmatrix launcher (cauchy_orig,
+ * cauchy_good) would launch for n_out outputs over n_src sources of
+ * chunk_bytes each, at word size w and packet size pkt, when the rows have
+ * n_ops set bits. knobs = the values of ECX_BITQ, ECX_BITW, ECX_BITREG,
+ * ECX_BITPIPE, ECX_BITT, ECX_BITXCD as given (unset: 16, 8, 2, 0, 256, 0);
+ * the clamps are applied here as in the launcher. out[0..15] =
+ *   0 kernel (0 LDS window, 1 register, 2 pipelined LDS window)
+ *   1 register kernel: accumulator rows NR   2 register kernel: positions
+ *   3 window bytes q      4 log2(q/16)       5 VQS instance (3/4/5, else -1)
+ *   6 LDS-DMA staging (0: through registers) 7 16 B items per window
+ *   8 windows per superword                  9 windows per chunk
+ *  10 windows per block  11 grid x           12 threads per block
+ *  13 dynamic LDS bytes  14 XCD mapping on   15 reserved (0)
+ * with 6..10, 13 and 14 zero for the register kernel. Returns ECX_OK, or
+ * ECX_ERR_INVAL exactly where the launcher refuses: n_src outside 1..16,
+ * n_out outside 1..8, w outside 1..8, pkt no positive multiple of 16,
+ * chunk_bytes no positive multiple of w*pkt (here also: 32 GiB or more), or
+ * more than 65535 set bits on the LDS kernels. */
+ECX_API int ecx_bitmatrix_plan_probe(const int knobs[6], int w, int pkt,
+                                     int n_src, int n_out, long n_ops,
+                                     size_t chunk_bytes, int out[16]);
+
 /* Replace the coding rows of the generator with a custom m x k matrix
  * (clears decode-plan caches). Lets composed codecs — SHEC's shingled
  * matrix (src/erasure-code/shec/ErasureCodeShec.cc:700-768), custom

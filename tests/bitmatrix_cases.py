@@ -1,6 +1,6 @@
 """References and case tables shared by test_kernel_references.py (CPU: the
-references against the oracle, the case geometry against the launcher's
-arithmetic) and test_gpu_bitmatrix_kernel.py, test_gpu_bitmatrix_knobs.py and
+references against the oracle, the case tables against geometry(), and
+geometry() against the launcher's plan probe) and test_gpu_bitmatrix_kernel.py, test_gpu_bitmatrix_knobs.py and
 test_gpu_w16_kernel.py (GPU: bytes). Not a test module. Everything is
 seeded; nothing here touches the GPU or the code under test.
 
@@ -130,14 +130,16 @@ def patterns(n, max_e):
 
 
 # ---------------------------------------------------------------------------
-# the bitmatrix launcher's arithmetic, restated from run_bitmatrix
+# the bitmatrix launcher's arithmetic, restated independently of its plan
+# (ceph_amd/csrc/bit_plan.cpp); test_kernel_references.py holds the two
+# against each other through ceph_amd.bitmatrix_plan_probe
 # ---------------------------------------------------------------------------
 
 def geometry(n_src, pkt, n_sw, n_out=2, accum=False, bitq=16, wpb=8,
              bitreg=2, pipe=0, xcd=0):
-    """What run_bitmatrix launches for n_src sources and n_out outputs of
-    n_sw superwords at packet size pkt under the given knob values (the
-    defaults are the launcher's). Returns a dict."""
+    """What the bitmatrix launcher launches for n_src sources and n_out
+    outputs of n_sw superwords at packet size pkt under the given knob
+    values (the defaults are the launcher's). Returns a dict."""
     use_reg = (n_out <= 4) if bitreg == 1 else (n_out == 1 and bitreg == 2)
     if use_reg:
         n_pos = n_sw * pkt // 16

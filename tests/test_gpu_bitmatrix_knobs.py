@@ -1,13 +1,15 @@
-"""The bitmatrix kernels under their knobs. In run_bitmatrix, ECX_BITREG,
-ECX_BITPIPE, ECX_BITT, ECX_BITW, ECX_BITQ, ECX_BITSTAGGER and ECX_BITXCD
-(and ECX_NT) select kernels, template instances and block mappings: the
+"""The bitmatrix kernels under their knobs. In the launcher's bit_plan(),
+ECX_BITREG, ECX_BITPIPE, ECX_BITT, ECX_BITW, ECX_BITQ and ECX_BITXCD (and, as
+launch arguments, ECX_BITSTAGGER and ECX_NT) select kernels, template
+instances and block mappings: the
 register kernel's NR = 16/24/32 instances and the whole of
 ec_bitmatrix_pipe_kernel are reached only through them. The knobs are read
 once per process, so each setting is checked in a child process of its own
 (that is what this test is about), bit-exact against bitmatrix_cases.ref_bit
 in the guarded form of test_gpu_bitmatrix_kernel.py. Every child runs all of
 bitmatrix_cases.KNOB_ENCODES / KNOB_DECODES / KNOB_DELTAS;
-test_kernel_references.py derives which instance each setting reaches. No
+test_kernel_references.py derives which instance each setting reaches and
+holds that derivation against the launcher's own plan. No
 setting needs more than 64 KiB of dynamic LDS. Run as a script, this file is
 the child."""
 import os

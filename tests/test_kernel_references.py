@@ -1,12 +1,15 @@
 """CPU checks of tests/bitmatrix_cases.py: the numpy references equal the
-oracle's own routines at every shape the GPU tests use, and the case tables
-reach the kernel instances they claim, by the launcher's arithmetic restated
-in bitmatrix_cases.geometry(). A later change of the launcher's defaults
-makes the tables fail here instead of silently no longer reaching an
-instance. Nothing here needs a GPU."""
+oracle's own routines at every shape the GPU tests use, the case tables reach
+the kernel instances they claim by the arithmetic restated in
+bitmatrix_cases.geometry(), and geometry() agrees with the plan the launcher
+itself launches by (ceph_amd.bitmatrix_plan_probe, the bit_plan() of
+run_bitmatrix) at every launch of the GPU files. A later change of the
+launcher's selection or defaults fails here instead of silently no longer
+reaching an instance. Nothing here needs a GPU."""
 import numpy as np
 import pytest
 
+import ceph_amd
 import oracle
 import bitmatrix_cases as cases
 
@@ -239,6 +242,140 @@ def test_knob_cases_reach_their_instances():
                   {"ECX_BITSTAGGER": "2"},
                   {"ECX_BITPIPE": "1", "ECX_NT": "0"}):
         assert other in K
+
+
+# ---- geometry() against the launcher's own plan ----
+# geometry() is an independent restatement; bitmatrix_plan_probe runs the
+# bit_plan() that run_bitmatrix launches by. While the two agree, a case that
+# geometry() says reaches an instance does reach it.
+
+REG_FIELDS = ("kernel", "nr", "n_pos", "grid")
+LDS_FIELDS = ("kernel", "grid", "q", "vqs", "staging", "items", "wps",
+              "n_windows", "xcdmap")
+
+
+def popcount(rows):
+    return int(np.count_nonzero(rows))
+
+
+def gf_inverse(a):
+    """Inverse of a square GF(2^8) matrix, by the oracle's field."""
+    n = len(a)
+    a = [[int(x) for x in row] + [int(i == j) for j in range(n)]
+         for i, row in enumerate(a)]
+    for c in range(n):
+        p = next(r for r in range(c, n) if a[r][c])
+        a[c], a[p] = a[p], a[c]
+        inv = oracle.gf_inv(a[c][c])
+        a[c] = [oracle.gf_mul(inv, x) for x in a[c]]
+        for r in range(n):
+            if r != c and a[r][c]:
+                f = a[r][c]
+                a[r] = [x ^ oracle.gf_mul(f, y) for x, y in zip(a[r], a[c])]
+    return [row[n:] for row in a]
+
+
+def decode_rows(tech, k, m, erased):
+    """Bit rows that rebuild the erased chunks from the first k present."""
+    gen = oracle.matrix(tech, k, m)
+    surv = [i for i in range(k + m) if i not in erased][:k]
+    inv = gf_inverse([gen[s] for s in surv])
+    rows = np.zeros((len(erased), k), np.uint8)
+    for j, e in enumerate(erased):
+        for c in range(k):
+            for i in range(k):
+                rows[j, c] ^= oracle.gf_mul(int(gen[e][i]), inv[i][c])
+    return oracle.bitmatrix(rows)
+
+
+def check_plan(g, knobs, n_src, pkt, n_sw, n_out, rows):
+    assert np.shape(rows) == (8 * n_out, 8 * n_src)
+    got = ceph_amd.bitmatrix_plan_probe(n_src, n_out, pkt, n_sw * 8 * pkt,
+                                        popcount(rows), knobs)
+    fields = REG_FIELDS if g["kernel"] == "reg" else LDS_FIELDS
+    assert {f: got[f] for f in fields} == {f: g[f] for f in fields}, \
+        (knobs, n_src, pkt, n_sw, n_out)
+    if g["kernel"] != "reg":
+        assert got["lds_bytes"] <= g["lds_bound"]
+
+
+def delta_rows(data, coding):
+    return cases.encode_rows("cauchy_orig", 3, 3)[
+        8 * (coding - 3):8 * (coding - 2), 8 * data:8 * data + 8]
+
+
+@pytest.mark.parametrize("knobs", [{}] + cases.KNOBS,
+                         ids=lambda kn: "-".join(
+                             f"{n[4:]}{v}" for n, v in kn.items()) or "default")
+def test_plan_probe_agrees_with_geometry_on_every_knob_launch(knobs):
+    want = iter(cases.knob_launches(knobs))
+    for tech, k, m, pkt, n_sw, _ in cases.KNOB_ENCODES:
+        g = cases.knob_geometry(knobs, k, pkt, n_sw, m)
+        assert g == next(want)
+        check_plan(g, knobs, k, pkt, n_sw, m, cases.encode_rows(tech, k, m))
+    for tech, k, m, pkt, n_sw, _, er in cases.KNOB_DECODES:
+        g = cases.knob_geometry(knobs, k, pkt, n_sw, len(er))
+        assert g == next(want)
+        check_plan(g, knobs, k, pkt, n_sw, len(er),
+                   decode_rows(tech, k, m, er))
+    for pkt, n_sw, data, coding in cases.KNOB_DELTAS:
+        g = cases.knob_geometry(knobs, 1, pkt, n_sw, 1, accum=True)
+        assert g == next(want)
+        check_plan(g, knobs, 1, pkt, n_sw, 1, delta_rows(data, coding))
+    assert next(want, None) is None
+
+
+def test_plan_probe_agrees_with_geometry_on_the_default_shapes():
+    for (k, pkt, n_sw) in cases.LDS_SHAPES:
+        for n_out in (1, 2, 3, 5, 8):
+            rows = cases.encode_rows("cauchy_orig", k, 8)[:8 * n_out]
+            check_plan(cases.geometry(k, pkt, n_sw, n_out=n_out), {}, k, pkt,
+                       n_sw, n_out, rows)
+    for k, m, pkt, n_sw in cases.REG_SHAPES:
+        rows = cases.encode_rows("cauchy_orig", k, m)
+        g = cases.geometry(k, pkt, n_sw, n_out=1)
+        assert g["kernel"] == "reg"
+        check_plan(g, {}, k, pkt, n_sw, 1, rows[:8])
+        check_plan(cases.geometry(1, pkt, n_sw, n_out=1, accum=True), {}, 1,
+                   pkt, n_sw, 1, rows[:8, :8])
+    for pkt, n_sw, data, coding in cases.KNOB_DELTAS:
+        check_plan(cases.geometry(1, pkt, n_sw, n_out=1, accum=True), {}, 1,
+                   pkt, n_sw, 1, delta_rows(data, coding))
+
+
+def test_plan_probe_clamps_like_the_launcher():
+    """ECX_BITQ 8..120, ECX_BITW 1..4096, ECX_BITT 64/128/256 else 256."""
+    def probe(**kn):
+        return ceph_amd.bitmatrix_plan_probe(16, 3, 2048, 8 * 2048, 700, kn)
+    assert probe(ECX_BITQ=1) == probe(ECX_BITQ=8)
+    assert probe(ECX_BITQ=999) == probe(ECX_BITQ=120)
+    # 16 sources: the new window's 128 * q bytes within the budget
+    assert [probe(ECX_BITQ=b)["q"] for b in (8, 16, 120)] == [64, 128, 512]
+    assert probe(ECX_BITW=0) == probe(ECX_BITW=1)
+    assert probe(ECX_BITW=5000)["wpb"] == 4096
+    assert [probe(ECX_BITT=t)["threads"] for t in (64, 128, 256, 96, 512)] \
+        == [64, 128, 256, 256, 256]
+    assert probe(ECX_BITPIPE=1, ECX_BITT=64)["threads"] == 256
+
+
+@pytest.mark.parametrize("n_src,n_out,pkt,chunk", [
+    (0, 3, 2048, 16384), (17, 3, 2048, 16384),
+    (4, 0, 2048, 16384), (4, 9, 2048, 16384),
+    (4, 3, 2048, 16384 + 2048), (4, 3, 2048, 0),
+    (4, 3, 8, 64), (4, 3, 24, 192),
+])
+def test_plan_probe_refuses_what_the_launcher_refuses(n_src, n_out, pkt,
+                                                      chunk):
+    with pytest.raises(ceph_amd.EcError, match="EINVAL"):
+        ceph_amd.bitmatrix_plan_probe(n_src, n_out, pkt, chunk, 100)
+
+
+def test_plan_probe_refuses_an_op_list_past_u16_on_the_lds_kernels_only():
+    with pytest.raises(ceph_amd.EcError, match="EINVAL"):
+        ceph_amd.bitmatrix_plan_probe(4, 2, 2048, 16384, 0x10000)
+    assert ceph_amd.bitmatrix_plan_probe(4, 2, 2048, 16384, 0xffff)
+    assert ceph_amd.bitmatrix_plan_probe(4, 1, 2048, 16384,
+                                         0x10000)["kernel"] == "reg"
 
 
 def test_w16_grids():
