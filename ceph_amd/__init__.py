@@ -110,6 +110,17 @@ def _lib():
         ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64),
         ctypes.c_long, ctypes.POINTER(ctypes.c_long),
         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    lib.ecx_verify_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_long, ctypes.c_size_t,
+                                     ctypes.c_uint64, ctypes.c_void_p,
+                                     ctypes.c_int]
+    lib.ecx_verify_plan_probe.argtypes = [
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+        ctypes.c_void_p]
+    lib.ecx_verify_chunks_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_uint64, ctypes.c_size_t,
+                                           ctypes.POINTER(ctypes.c_uint64)]
     lib.ecx_bitmatrix_plan_probe.argtypes = [
         ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_size_t,
@@ -262,6 +273,23 @@ def update_plan_probe(k, m, masks):
         act.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
         ctypes.byref(n_act)), "ecx_update_plan_probe")
     return r, base[:len(a)], act[:n_act.value]
+
+
+def verify_plan_probe(technique, k, m, present_mask):
+    """CPU-only: how verify_batch would plan this present mask. Returns
+    (survivors, checked, rows): the first k present chunk ids, the remaining
+    present ids ascending, and one coefficient row per checked chunk over
+    the survivors (an (n_checked, k) uint8 array)."""
+    t = TECHNIQUES[technique] if isinstance(technique, str) else technique
+    sv = np.zeros(max(k, 1), dtype=np.int32)
+    ck = np.zeros(max(m, 1), dtype=np.int32)
+    rows = np.zeros((max(m, 1), max(k, 1)), dtype=np.uint8)
+    n = _ck(lib().ecx_verify_plan_probe(
+        t, k, m, present_mask,
+        sv.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+        ck.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+        rows.ctypes.data_as(ctypes.c_void_p)), "ecx_verify_plan_probe")
+    return sv[:k], ck[:n], rows.reshape(-1)[:n * k].reshape(n, k)
 
 
 _BIT_KNOBS = (("ECX_BITQ", 16), ("ECX_BITW", 8), ("ECX_BITREG", 2),
@@ -437,6 +465,30 @@ class EcContext:
         _ck(lib().ecx_update_batch(self._h, dptr, n_stripes, chunk_bytes,
                                    d_new, _u64p(a), slot), "ecx_update_batch")
 
+    def verify_batch(self, dptr, n_stripes, chunk_bytes, present_mask=None,
+                     d_bad=None, slot=0):
+        """Consistency check of a batch: the first k present chunks of each
+        stripe vouch for every further present one. Returns a uint64 array
+        of n_stripes words, bit i of word s set when checked chunk i of
+        stripe s differs from its recomputed value. present_mask None = all
+        k+m chunks; d_bad None = a temporary device array of n_stripes
+        words. The batch is only read."""
+        if present_mask is None:
+            present_mask = (1 << (self.k + self.m)) - 1
+        words = np.zeros(max(int(n_stripes), 0), dtype=np.uint64)
+        own = d_bad is None
+        if own:
+            d_bad = self.dbuf_alloc(max(words.nbytes, 8))
+        try:
+            _ck(lib().ecx_verify_batch(self._h, dptr, n_stripes, chunk_bytes,
+                                       present_mask, d_bad, slot),
+                "ecx_verify_batch")
+            self.download(words, d_bad, slot)
+        finally:
+            if own:
+                self.dbuf_free(d_bad)
+        return words
+
     def matmul_batch(self, dptr, n_stripes, chunk_bytes, src_ids, out_ids,
                      rows, slot=0):
         """Generic device-batch GF matmul over chunk ids (LRC layer
@@ -497,6 +549,30 @@ class EcContext:
         _ck(lib().ecx_decode_chunks_host(self._h, _ptr_array(chunks), mask, n),
             "ecx_decode_chunks_host")
         return chunks
+
+    def verify_chunks(self, chunks, present=None):
+        """chunks: list of k+m uint8 arrays of one stripe (entries of absent
+        ids are ignored and may be None). Returns the stripe's word as an
+        int: bit i set when checked chunk i differs from its value
+        recomputed from the first k present chunks. A present entry that is
+        None raises EINVAL."""
+        if present is None:
+            present = [True] * (self.k + self.m)
+        mask = 0
+        for i, p in enumerate(present):
+            if p:
+                mask |= 1 << i
+        sizes = {c.nbytes for c, p in zip(chunks, present)
+                 if p and c is not None}
+        if len(sizes) > 1:
+            raise EcError("ecx_verify_chunks_host: equal-length chunks "
+                          f"required, got sizes {sorted(sizes)}")
+        word = ctypes.c_uint64()
+        _ck(lib().ecx_verify_chunks_host(
+            self._h, _ptr_array(list(chunks)), mask,
+            sizes.pop() if sizes else 0, ctypes.byref(word)),
+            "ecx_verify_chunks_host")
+        return word.value
 
     def encode_delta(self, old, new):
         delta = np.zeros_like(old)

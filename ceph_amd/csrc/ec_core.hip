@@ -32,6 +32,7 @@
 
 
 #include <atomic>
+#include <cstddef>
 #include <cstdint>
 #include <algorithm>
 #include <cstring>
@@ -49,6 +50,7 @@
 #include "gf.h"
 #include "decode_multi.h"
 #include "update_plan.h"
+#include "verify_plan.h"
 #include "bit_plan.h"
 #include "stream_walk.h"
 
@@ -254,10 +256,17 @@ struct EcStreamParams {
   // coefficient is not a general one
   uint32_t tabs[ECX_MAX_K][ECX_STREAM_MAX_OUT][5];
   int n_src;
+  // ec_gf_verify_kernel only: chunk id of each output (< 64), the bit it
+  // reports under. Sits in what was tail padding, so the block keeps its size
+  // and the stream kernel its argument layout.
+  uint8_t out_id[ECX_STREAM_MAX_OUT];
 };
 static_assert(sizeof(EcStreamParams) <= 4096,
               "EcStreamParams must fit the kernel argument segment");
 static_assert(ECX_MAX_K <= 32, "source classes are 32-bit masks");
+static_assert(offsetof(EcStreamParams, out_id) + ECX_STREAM_MAX_OUT ==
+                  sizeof(EcStreamParams),
+              "out_id fills the tail padding");
 
 // One source's contribution to every output accumulator. The byte is split
 // into the contiguous bit groups 0-2, 3-5, 6-7 (5 VALU per dword):
@@ -302,6 +311,50 @@ __device__ __forceinline__ void ecx_stream_source(
   }
 }
 
+// All n_src sources of one tile position (sb = tile base, voff = the lane's
+// 16 B) into the accumulators: the source loop of ec_gf_stream_kernel and
+// ec_gf_verify_kernel.
+// One-ahead prefetch over two load buffers used alternately: the load of
+// source i + 1 is in flight while source i is computed. Every load in the
+// loop is unconditional (the last one or two sources are peeled), so each
+// wait leaves exactly one load outstanding, and no loaded register is ever
+// copied (a copy would wait for its load). The offset of the load after next
+// is fetched (a scalar load) while the current one is issued, and the
+// scheduling barrier keeps each vector load ahead of the compute it
+// overlaps: without it the compiler hoists the compute's head above the load
+// to cover the offset fetch, and the wait for the previous load goes with it.
+template <int NOUT>
+__device__ __forceinline__ void ecx_stream_sources(
+    const EcStreamParams& p, const uint32_t (&one_mask)[NOUT],
+    const uint32_t (&mul_mask)[NOUT], int n_src, const uint8_t* sb,
+    uint32_t voff, uint32_t (&acc)[NOUT][4]) {
+#define ECX_STREAM_LD(dst_, next_)                                        \
+  do {                                                                    \
+    dst_ = __builtin_nontemporal_load(                                    \
+        reinterpret_cast<const v4u*>(sb + so + voff));                    \
+    so = p.src_off[next_];                                                \
+    __builtin_amdgcn_sched_barrier(0);                                    \
+  } while (0)
+  uint64_t so = p.src_off[0];
+  v4u d0, d1;
+  ECX_STREAM_LD(d0, 1);
+  int i = 0;
+  for (; i + 2 < n_src; i += 2) {
+    ECX_STREAM_LD(d1, i + 2);
+    ecx_stream_source<NOUT>(p, one_mask, mul_mask, i, d0, acc);
+    ECX_STREAM_LD(d0, i + 3);  // src_off is padded: index <= n_src + 1
+    ecx_stream_source<NOUT>(p, one_mask, mul_mask, i + 1, d1, acc);
+  }
+  if (i + 1 < n_src) {
+    ECX_STREAM_LD(d1, 0);
+    ecx_stream_source<NOUT>(p, one_mask, mul_mask, i, d0, acc);
+    ecx_stream_source<NOUT>(p, one_mask, mul_mask, i + 1, d1, acc);
+  } else {
+    ecx_stream_source<NOUT>(p, one_mask, mul_mask, i, d0, acc);
+  }
+#undef ECX_STREAM_LD
+}
+
 // A tile is 256 lanes x 16 B of one chunk position range of one stripe.
 // Which tiles a block takes, and in which order, is the walk of
 // stream_walk.h: every value of it is launch-uniform and host-computed, the
@@ -336,41 +389,7 @@ __global__ __launch_bounds__(256, NOUT < 4 ? 8 : 6) void ec_gf_stream_kernel(
 #pragma unroll
       for (int j = 0; j < NOUT; j++)
         acc[j][0] = acc[j][1] = acc[j][2] = acc[j][3] = 0u;
-      // one-ahead prefetch over two load buffers used alternately: the load
-      // of source i + 1 is in flight while source i is computed. Every load
-      // in the loop is unconditional (the last one or two sources are
-      // peeled), so each wait leaves exactly one load outstanding, and no
-      // loaded register is ever copied (a copy would wait for its load).
-      // The offset of the load after next is fetched (a scalar load) while
-      // the current one is issued, and the scheduling barrier keeps each
-      // vector load ahead of the compute it overlaps: without it the
-      // compiler hoists the compute's head above the load to cover the
-      // offset fetch, and the wait for the previous load goes with it.
-#define ECX_STREAM_LD(dst_, next_)                                        \
-  do {                                                                    \
-    dst_ = __builtin_nontemporal_load(                                    \
-        reinterpret_cast<const v4u*>(sb + so + voff));                    \
-    so = p.src_off[next_];                                                \
-    __builtin_amdgcn_sched_barrier(0);                                    \
-  } while (0)
-      uint64_t so = p.src_off[0];
-      v4u d0, d1;
-      ECX_STREAM_LD(d0, 1);
-      int i = 0;
-      for (; i + 2 < n_src; i += 2) {
-        ECX_STREAM_LD(d1, i + 2);
-        ecx_stream_source<NOUT>(p, one_mask, mul_mask, i, d0, acc);
-        ECX_STREAM_LD(d0, i + 3);  // src_off is padded: index <= n_src + 1
-        ecx_stream_source<NOUT>(p, one_mask, mul_mask, i + 1, d1, acc);
-      }
-      if (i + 1 < n_src) {
-        ECX_STREAM_LD(d1, 0);
-        ecx_stream_source<NOUT>(p, one_mask, mul_mask, i, d0, acc);
-        ecx_stream_source<NOUT>(p, one_mask, mul_mask, i + 1, d1, acc);
-      } else {
-        ecx_stream_source<NOUT>(p, one_mask, mul_mask, i, d0, acc);
-      }
-#undef ECX_STREAM_LD
+      ecx_stream_sources<NOUT>(p, one_mask, mul_mask, n_src, sb, voff, acc);
       uint8_t* ob = obuf + tbase;
 #pragma unroll
       for (int j = 0; j < NOUT; j++) {
@@ -378,6 +397,72 @@ __global__ __launch_bounds__(256, NOUT < 4 ? 8 : 6) void ec_gf_stream_kernel(
         o.x = acc[j][0]; o.y = acc[j][1]; o.z = acc[j][2]; o.w = acc[j][3];
         __builtin_nontemporal_store(
             o, reinterpret_cast<v4u*>(ob + p.out_off[j] + voff));
+      }
+    }
+    ecx_walk_next(walk, pos);
+  }
+}
+
+// Consistency check (ecx_verify_batch): the stream kernel
+// with another epilogue. The NOUT "outputs" are stored chunks; each is
+// recomputed from the sources as above, then the stored vector is loaded and
+// compared where the stream kernel would store. A wave in which any lane
+// differs sets bit out_id[j] of the stripe's word with one atomicOr from one
+// lane; a clean tile issues no atomic and no store at all. The batch is only
+// read. bad[] is zeroed by the host ahead of the launch.
+// The ballot sits inside the tile guard, so lanes beyond the chunk (partial
+// last tile) and the skipped end of a narrow last stripe group do not vote.
+// The stored chunks are not sources: they are loaded by out_off after the
+// source loop, when its two load buffers are free, so k = 32 keeps its 32
+// source-class bits.
+template <int NOUT>
+__global__ __launch_bounds__(256, NOUT < 4 ? 8 : 6) void ec_gf_verify_kernel(
+    const uint8_t* buf, unsigned long long* bad, const EcStreamParams p,
+    uint64_t stripe_bytes, uint64_t vecs_per_chunk, const EcxWalk walk) {
+  const uint32_t voff = threadIdx.x << 4;
+  const int n_src = p.n_src;
+  uint32_t one_mask[NOUT], mul_mask[NOUT];
+#pragma unroll
+  for (int j = 0; j < NOUT; j++) {
+    one_mask[j] = p.one_mask[j];
+    mul_mask[j] = p.mul_mask[j];
+  }
+  EcxWalkPos pos = ecx_walk_start(walk, blockIdx.x);
+  while (ecx_walk_live(walk, pos)) {
+    const uint32_t stripe = ecx_walk_stripe(walk, pos);
+    const uint32_t tile = pos.t;
+    const uint64_t tbase =
+        (uint64_t)stripe * stripe_bytes + ((uint64_t)tile << 12);
+    if (stripe < walk.n_stripes &&
+        ((uint64_t)tile << 8) + threadIdx.x < vecs_per_chunk) {
+      const uint8_t* sb = buf + tbase;
+      uint32_t acc[NOUT][4];
+#pragma unroll
+      for (int j = 0; j < NOUT; j++)
+        acc[j][0] = acc[j][1] = acc[j][2] = acc[j][3] = 0u;
+      ecx_stream_sources<NOUT>(p, one_mask, mul_mask, n_src, sb, voff, acc);
+      // all NOUT stored vectors in flight together, then compared
+      v4u st[NOUT];
+#pragma unroll
+      for (int j = 0; j < NOUT; j++)
+        st[j] = __builtin_nontemporal_load(
+            reinterpret_cast<const v4u*>(sb + p.out_off[j] + voff));
+#pragma unroll
+      for (int j = 0; j < NOUT; j++) {
+        const uint32_t diff = (acc[j][0] ^ st[j].x) | (acc[j][1] ^ st[j].y) |
+                              (acc[j][2] ^ st[j].z) | (acc[j][3] ^ st[j].w);
+        // wave-uniform, so the branch is scalar
+        const unsigned long long vote = __ballot(diff != 0u);
+        if (vote != 0ull) {
+          // The bit is formed behind the branch: the empty asm keeps the
+          // compiler from hoisting 1 << id out of the tile loop into a VGPR
+          // pair per output, which is 12 B/lane of scratch at NOUT = 3.
+          uint32_t id = p.out_id[j];
+          asm volatile("" : "+s"(id));
+          // the first differing lane (it voted, so it is active) reports
+          if ((threadIdx.x & 63u) == (uint32_t)__ffsll((long long)vote) - 1u)
+            atomicOr(&bad[stripe], 1ull << id);
+        }
       }
     }
     ecx_walk_next(walk, pos);
@@ -1188,6 +1273,9 @@ struct ecx_ctx {
   // blocks per CU for NOUT 1..4 (the persistent grid, ECX_STREAM_BPC=0)
   std::atomic<int> stream_cus{0};
   std::atomic<int> stream_occ[5] = {};
+  // the same for ec_gf_verify_kernel, whose instances need not stay resident
+  // in the same numbers
+  std::atomic<int> verify_occ[5] = {};
 
   bool is_bitmatrix() const {
     return technique == ECX_T_CAUCHY_ORIG_JERASURE ||
@@ -1741,15 +1829,17 @@ static int env_stream_xcd() {
 }
 
 template <int NO>
-static hipError_t stream_occupancy(int* n) {
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(
-      n, ec_gf_stream_kernel<NO>, 256, 0);
+static hipError_t stream_occupancy(int* n, bool verify) {
+  return verify ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                      n, ec_gf_verify_kernel<NO>, 256, 0)
+                : hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                      n, ec_gf_stream_kernel<NO>, 256, 0);
 }
 
 // Grid size for n_tiles tiles (see ECX_STREAM_BPC). Both runtime figures
-// (CU count, resident blocks per CU of the NOUT instance) are cached in the
-// context.
-static int stream_grid(ecx_ctx* ctx, int n_out, uint64_t n_tiles,
+// (CU count, resident blocks per CU of the NOUT instance of the stream or the
+// verify kernel) are cached in the context.
+static int stream_grid(ecx_ctx* ctx, bool verify, int n_out, uint64_t n_tiles,
                        uint32_t* grid) {
   int cus = ctx->stream_cus.load();
   if (cus <= 0) {
@@ -1764,15 +1854,17 @@ static int stream_grid(ecx_ctx* ctx, int n_out, uint64_t n_tiles,
     g = n_tiles;
   } else {
     if (bpc == 0) {
-      bpc = ctx->stream_occ[n_out].load();
+      std::atomic<int>& occ =
+          verify ? ctx->verify_occ[n_out] : ctx->stream_occ[n_out];
+      bpc = occ.load();
       if (bpc <= 0) {
-        hipError_t e = n_out == 1   ? stream_occupancy<1>(&bpc)
-                       : n_out == 2 ? stream_occupancy<2>(&bpc)
-                       : n_out == 3 ? stream_occupancy<3>(&bpc)
-                                    : stream_occupancy<4>(&bpc);
+        hipError_t e = n_out == 1   ? stream_occupancy<1>(&bpc, verify)
+                       : n_out == 2 ? stream_occupancy<2>(&bpc, verify)
+                       : n_out == 3 ? stream_occupancy<3>(&bpc, verify)
+                                    : stream_occupancy<4>(&bpc, verify);
         HIP_TRY(e);
         bpc = std::max(1, bpc);
-        ctx->stream_occ[n_out].store(bpc);
+        occ.store(bpc);
       }
     }
     g = (uint64_t)cus * (uint64_t)bpc;
@@ -1784,27 +1876,37 @@ static int stream_grid(ecx_ctx* ctx, int n_out, uint64_t n_tiles,
   return ECX_OK;
 }
 
-// Launch ec_gf_stream_kernel for one output group (n_out <= 4). coeff is
-// n_out x n_src. Nothing is staged on the device: the argument block is the
-// launch's own kernarg.
-static int launch_stream(ecx_ctx* ctx, Slot& s, const uint8_t* d_buf,
-                         uint8_t* d_obuf, const int* src_ids, int n_src,
-                         const int* out_ids, int n_out, const uint8_t* coeff,
-                         const bool* src_null, long n_stripes,
-                         size_t chunk_bytes, bool time_it) {
+// Everything a launch of ec_gf_stream_kernel or ec_gf_verify_kernel passes
+// besides its pointers.
+struct StreamLaunch {
+  EcStreamParams p;
+  uint64_t stripe_bytes, vecs;
+  uint32_t grid;
+  EcxWalk walk;
+};
+
+// Argument block, grid and walk for one output group (n_out <= 4) of the
+// stream kernel or, with `verify`, of the verify kernel, where the outputs
+// are the checked chunks. coeff is n_out x n_src.
+static int stream_prepare(ecx_ctx* ctx, bool verify, const int* src_ids,
+                          int n_src, const int* out_ids, int n_out,
+                          const uint8_t* coeff, const bool* src_null,
+                          long n_stripes, size_t chunk_bytes,
+                          StreamLaunch& L) {
   if (chunk_bytes % 16 || n_stripes <= 0 || n_stripes > 65535 || n_out < 1 ||
       n_out > ECX_STREAM_MAX_OUT)
     return ECX_ERR_INVAL;
   HIP_TRY(hipSetDevice(ctx->device));
 
   const ecx::GF8& f = ecx::gf8();
-  EcStreamParams p;
+  EcStreamParams& p = L.p;
   std::memset(&p, 0, sizeof(p));
   p.n_src = n_src;
   for (int i = 0; i < n_src; i++)
     p.src_off[i] = (uint64_t)src_ids[i] * chunk_bytes;
   for (int j = 0; j < n_out; j++) {
     p.out_off[j] = (uint64_t)out_ids[j] * chunk_bytes;
+    p.out_id[j] = (uint8_t)out_ids[j];
     for (int i = 0; i < n_src; i++) {
       const uint8_t c = coeff[(size_t)j * n_src + i];
       if (c == 0 || (src_null && src_null[i])) continue;
@@ -1817,23 +1919,37 @@ static int launch_stream(ecx_ctx* ctx, Slot& s, const uint8_t* d_buf,
     }
   }
 
-  const uint64_t vecs = chunk_bytes >> 4;
-  const uint64_t tpc = (vecs + 255) / 256;  // tiles per chunk
+  L.vecs = chunk_bytes >> 4;
+  const uint64_t tpc = (L.vecs + 255) / 256;  // tiles per chunk
   const uint64_t n_tiles = tpc * (uint64_t)n_stripes;
-  uint32_t grid = 1;
-  int r = stream_grid(ctx, n_out, n_tiles, &grid);
+  L.grid = 1;
+  int r = stream_grid(ctx, verify, n_out, n_tiles, &L.grid);
   if (r != ECX_OK) return r;
   int width = env_stream_w();
   if (width < 1) width = env_stream_order() == 1 ? (int)n_stripes : 1;
-  const EcxWalk walk =
+  L.walk =
       ecx_walk_make((uint32_t)n_stripes, (uint32_t)std::max<uint64_t>(1, tpc),
-                    (uint32_t)width, env_stream_xcd() == 1, grid);
-  const uint64_t stripe_bytes = (uint64_t)(ctx->k + ctx->m) * chunk_bytes;
+                    (uint32_t)width, env_stream_xcd() == 1, L.grid);
+  L.stripe_bytes = (uint64_t)(ctx->k + ctx->m) * chunk_bytes;
+  return ECX_OK;
+}
 
+// Launch ec_gf_stream_kernel for one output group (n_out <= 4). Nothing is
+// staged on the device: the argument block is the launch's own kernarg.
+static int launch_stream(ecx_ctx* ctx, Slot& s, const uint8_t* d_buf,
+                         uint8_t* d_obuf, const int* src_ids, int n_src,
+                         const int* out_ids, int n_out, const uint8_t* coeff,
+                         const bool* src_null, long n_stripes,
+                         size_t chunk_bytes, bool time_it) {
+  StreamLaunch L;
+  int r = stream_prepare(ctx, false, src_ids, n_src, out_ids, n_out, coeff,
+                         src_null, n_stripes, chunk_bytes, L);
+  if (r != ECX_OK) return r;
   HIP_TRY(timer_start(s, time_it));
   dispatch_nout(n_out, [&](auto NO) {
-    hipLaunchKernelGGL((ec_gf_stream_kernel<NO()>), dim3(grid), dim3(256), 0,
-                       s.stream, d_buf, d_obuf, p, stripe_bytes, vecs, walk);
+    hipLaunchKernelGGL((ec_gf_stream_kernel<NO()>), dim3(L.grid), dim3(256),
+                       0, s.stream, d_buf, d_obuf, L.p, L.stripe_bytes,
+                       L.vecs, L.walk);
   });
   HIP_TRY(hipGetLastError());
   HIP_TRY(timer_stop(s, time_it));
@@ -2304,6 +2420,77 @@ static void multi_fill_recs(EcMultiRec* recs, const ecx::MultiGrouping& g,
   }
 }
 
+// ---- consistency check: host side ----
+static_assert(ECX_STREAM_MAX_OUT == ecx::VERIFY_MAX_OUT,
+              "kernel/verify-plan split");
+
+static int verify_err(ecx::VerifyStatus st) {
+  return st == ecx::VERIFY_OK      ? ECX_OK
+         : st == ecx::VERIFY_INVAL ? ECX_ERR_INVAL
+                                   : ECX_ERR_IO;
+}
+
+// What both verify calls refuse about the context and the shape (the tile
+// counters of the kernel are 32-bit, as for the stream kernel).
+static int verify_check_args(const ecx_ctx* ctx, long n_stripes,
+                             size_t chunk_bytes) {
+  if (!ctx->is_table8() || chunk_bytes == 0 || chunk_bytes % 16 ||
+      (chunk_bytes >> 12) >= 0x7fffffffull || n_stripes <= 0 ||
+      n_stripes > 65535)
+    return ECX_ERR_INVAL;
+  return ECX_OK;
+}
+
+// Verify plan of a mask (verify_plan.h), its decode plan through the LRU.
+static int get_verify_plan(ecx_ctx* ctx, uint64_t present_mask,
+                           ecx::VerifyPlan& vp) {
+  auto resolve = [&](uint64_t mask, std::vector<int>& sv, std::vector<int>& er,
+                     std::vector<uint8_t>& rw) {
+    DecodePlan dp;
+    if (get_decode_plan(ctx, mask, dp) != ECX_OK) return false;
+    sv = std::move(dp.survivors);
+    er = std::move(dp.erased);
+    rw = std::move(dp.rows);
+    return true;
+  };
+  return verify_err(
+      ecx::plan_verify(ctx->k, ctx->m, present_mask, resolve, vp));
+}
+
+// Zero d_bad, then check the plan's chunks in passes of <= 4, back to back
+// under one event pair. Arguments are validated and the slot is locked by the
+// caller; every pass is prepared before anything is enqueued.
+static int run_verify(ecx_ctx* ctx, Slot& s, const uint8_t* d_buf,
+                      long n_stripes, size_t chunk_bytes,
+                      const ecx::VerifyPlan& vp, uint64_t* d_bad) {
+  const int k = ctx->k, n = (int)vp.checked.size();
+  std::vector<StreamLaunch> passes((size_t)(n + ECX_STREAM_MAX_OUT - 1) /
+                                   ECX_STREAM_MAX_OUT);
+  for (int j0 = 0; j0 < n; j0 += ECX_STREAM_MAX_OUT) {
+    int r = stream_prepare(ctx, true, vp.survivors.data(), k,
+                           vp.checked.data() + j0,
+                           std::min(ECX_STREAM_MAX_OUT, n - j0),
+                           vp.rows.data() + (size_t)j0 * k, nullptr, n_stripes,
+                           chunk_bytes, passes[j0 / ECX_STREAM_MAX_OUT]);
+    if (r != ECX_OK) return r;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemsetAsync(d_bad, 0, (size_t)n_stripes * 8, s.stream));
+  if (n == 0) return ECX_OK;  // nothing to check: zeros, nothing launched
+  HIP_TRY(timer_start(s));
+  for (int j0 = 0; j0 < n; j0 += ECX_STREAM_MAX_OUT) {
+    const StreamLaunch& L = passes[j0 / ECX_STREAM_MAX_OUT];
+    dispatch_nout(std::min(ECX_STREAM_MAX_OUT, n - j0), [&](auto NO) {
+      hipLaunchKernelGGL((ec_gf_verify_kernel<NO()>), dim3(L.grid), dim3(256),
+                         0, s.stream, d_buf, (unsigned long long*)d_bad, L.p,
+                         L.stripe_bytes, L.vecs, L.walk);
+    });
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(timer_stop(s));
+  return ECX_OK;
+}
+
 extern "C" {
 
 int ecx_encode_batch(ecx_ctx* ctx, void* dptr, long n_stripes,
@@ -2672,6 +2859,54 @@ int ecx_update_plan_probe(int k, int m, const uint64_t* write_masks, long n,
   std::copy(plan.active.begin(), plan.active.end(), active);
   *n_active = (int)plan.active.size();
   return plan.launches;
+}
+
+int ecx_verify_batch(ecx_ctx* ctx, const void* dptr, long n_stripes,
+                     size_t chunk_bytes, uint64_t present_mask,
+                     uint64_t* d_bad, int slot) {
+  if (!ctx || !dptr || !d_bad || slot < 0 || slot >= (int)ctx->slots.size())
+    return ECX_ERR_INVAL;
+  int r = verify_check_args(ctx, n_stripes, chunk_bytes);
+  if (r != ECX_OK) return r;
+  if ((uintptr_t)d_bad & 7) return ECX_ERR_INVAL;
+  // the words are written while the batch is read: no overlap
+  const uintptr_t b0 = (uintptr_t)dptr, w0 = (uintptr_t)d_bad;
+  const uintptr_t b1 =
+      b0 + (uintptr_t)n_stripes * (ctx->k + ctx->m) * chunk_bytes;
+  const uintptr_t w1 = w0 + (uintptr_t)n_stripes * 8;
+  if (w0 < b1 && b0 < w1) return ECX_ERR_INVAL;
+  ecx::VerifyPlan vp;
+  r = get_verify_plan(ctx, present_mask, vp);
+  if (r != ECX_OK) return r;
+  Slot& s = ctx->slots[slot];
+  std::lock_guard<std::recursive_mutex> g(s.mu);
+  return run_verify(ctx, s, (const uint8_t*)dptr, n_stripes, chunk_bytes, vp,
+                    d_bad);
+}
+
+int ecx_verify_plan_probe(int technique, int k, int m, uint64_t present_mask,
+                          int* survivors, int* checked, uint8_t* rows) {
+  // CPU-only: the planning ecx_verify_batch performs (same plan_verify, the
+  // decode plan composed directly instead of via a context's LRU). Outputs
+  // are written only on success.
+  if (!survivors || !checked || !rows || k < 1 || m < 1 || k + m > 64)
+    return ECX_ERR_INVAL;
+  if (technique != ECX_T_RS_VAN_ISA && technique != ECX_T_CAUCHY_ISA &&
+      technique != ECX_T_RS_VAN_JERASURE)
+    return ECX_ERR_INVAL;  // w=8 matrix techniques only, like the calls
+  std::vector<uint8_t> gen;
+  if (!ecx::gen_matrix(technique, gen, k, m)) return ECX_ERR_INVAL;
+  auto resolve = [&](uint64_t mask, std::vector<int>& sv, std::vector<int>& er,
+                     std::vector<uint8_t>& rw) {
+    return ecx::compose_decode_rows(gen, k, m, mask, sv, er, rw);
+  };
+  ecx::VerifyPlan vp;
+  const int r = verify_err(ecx::plan_verify(k, m, present_mask, resolve, vp));
+  if (r != ECX_OK) return r;
+  std::copy(vp.survivors.begin(), vp.survivors.end(), survivors);
+  std::copy(vp.checked.begin(), vp.checked.end(), checked);
+  std::copy(vp.rows.begin(), vp.rows.end(), rows);
+  return (int)vp.checked.size();
 }
 
 int ecx_bitmatrix_plan_probe(const int knobs[6], int w, int pkt, int n_src,
@@ -3456,6 +3691,46 @@ int ecx_decode_chunks_host(ecx_ctx* ctx, uint8_t* const* chunks,
   r = job_from_plan(ctx, plan, chunks, chunk_bytes, job);
   if (r != ECX_OK) return r;
   return host_call(ctx, si, job);
+}
+
+int ecx_verify_chunks_host(ecx_ctx* ctx, const uint8_t* const* chunks,
+                           uint64_t present_mask, size_t chunk_bytes,
+                           uint64_t* bad) {
+  if (!ctx || !chunks || !bad) return ECX_ERR_INVAL;
+  int r = verify_check_args(ctx, 1, chunk_bytes);
+  if (r != ECX_OK) return r;
+  ecx::VerifyPlan vp;
+  r = get_verify_plan(ctx, present_mask, vp);
+  if (r != ECX_OK) return r;
+  // unlike decode, a present chunk that is not given cannot be vouched for
+  const int cps = ctx->k + ctx->m;
+  for (int i = 0; i < cps; i++)
+    if ((present_mask >> i & 1) && !chunks[i]) return ECX_ERR_INVAL;
+  const int si = (int)(ctx->rr++ % ctx->slots.size());
+  Slot& s = ctx->slots[si];
+  std::lock_guard<std::recursive_mutex> g(s.mu);
+  // one stripe in the staging buffer, its word behind it (8-byte aligned:
+  // chunk_bytes is a multiple of 16); absent positions stay unwritten and
+  // are never read
+  const size_t cb = chunk_bytes, word_off = (size_t)cps * cb;
+  r = ensure_stage(ctx, s, word_off + 8);
+  if (r != ECX_OK) return r;
+  HIP_TRY(hipSetDevice(ctx->device));
+  for (int i = 0; i < cps; i++)
+    if (present_mask >> i & 1)
+      HIP_TRY(hipMemcpyAsync(s.d_stage + (size_t)i * cb, chunks[i], cb,
+                             hipMemcpyHostToDevice, s.stream));
+  uint64_t* d_word = (uint64_t*)(s.d_stage + word_off);
+  r = run_verify(ctx, s, s.d_stage, 1, cb, vp, d_word);
+  if (r != ECX_OK) {
+    (void)hipStreamSynchronize(s.stream);  // quiesce before buffer reuse
+    return r;
+  }
+  uint64_t word = 0;
+  HIP_TRY(hipMemcpyAsync(&word, d_word, 8, hipMemcpyDeviceToHost, s.stream));
+  HIP_TRY(wait_stream(s.stream));
+  *bad = word;
+  return ECX_OK;
 }
 
 int ecx_matmul_chunks_host(ecx_ctx* ctx, const uint8_t* const* srcs,

@@ -20,6 +20,9 @@
  *     -> ecx_apply_delta()                           (whole call fused:
  *                                                    ecx_apply_deltas_host; over a
  *                                                    batch: ecx_update_batch)
+ *   scrub's re-encode-and-compare (encode_chunks     src/erasure-code/ErasureCodeInterface.h
+ *     into a second buffer, then a compare pass)       encode_chunks, as used by the OSD
+ *     -> ecx_verify_batch()                            scrub path
  *   minimum_to_decode survivor choice                src/erasure-code/ErasureCode.cc:154-170
  *     -> ecx_minimum_to_decode()
  *   get_chunk_size / get_alignment                   ErasureCodeIsa.cc:65-79,
@@ -267,6 +270,46 @@ ECX_API int ecx_update_plan_probe(int k, int m, const uint64_t *write_masks,
                                   long n, long *new_base, int *active,
                                   int *n_active);
 
+/* ---------------- consistency check (scrub) --------------------------------
+ * Are the stored chunks still consistent with each other? The reference has
+ * no call for it: deep scrub and the check after recovery re-encode the
+ * stripe into a second buffer and compare (encode_chunks of
+ * ErasureCodeInterface.h as used by the OSD scrub path), which costs another
+ * m/(k+m) of the allocation and a second pass over the parities. This call
+ * only reads: k + (checked chunks) chunk reads per stripe and one 8-byte
+ * word written. dptr is the standard batch buffer; present_mask bit i set =>
+ * chunk i of every stripe is held. The first k present chunks in id order
+ * are the survivors (the rule of ecx_decode_batch, ErasureCode.cc:154-170)
+ * and determine the stripe; every further present chunk, data or parity, is
+ * checked: recomputed from the survivors and compared with what is stored.
+ * d_bad is a device array of n_stripes 64-bit words, 8-byte aligned and
+ * outside the batch. On success every word has been written: bit i of
+ * d_bad[s] is set exactly when checked chunk i of stripe s differs in at
+ * least one byte from its recomputed value; bits of survivors and of absent
+ * chunks are always 0. A mask of exactly k chunks checks nothing: zeros,
+ * nothing launched. The batch is never written. ceil(checked/4) launches
+ * back to back; ecx_last_kernel_ms covers the whole call (first launch to
+ * last). All validation precedes any GPU work: ECX_ERR_INVAL for a NULL
+ * pointer, bad slot, chunk_bytes 0 or not a multiple of 16, n_stripes
+ * outside 1..65535, d_bad not 8-byte aligned, a d_bad range that intersects
+ * the batch, a mask bit at position k+m or above, or a bitmatrix or w=16
+ * context (as for ecx_*_slices, *_multi and ecx_update_batch); ECX_ERR_IO
+ * for fewer than k present chunks or survivors that do not invert (possible
+ * after ecx_set_matrix). A refused call writes nothing to d_bad. */
+ECX_API int ecx_verify_batch(ecx_ctx *ctx, const void *dptr, long n_stripes,
+                             size_t chunk_bytes, uint64_t present_mask,
+                             uint64_t *d_bad, int slot);
+/* CPU-only (no GPU context): the planning of the call above. survivors[k] =
+ * the first k set bits of the mask; checked[] = the remaining set bits,
+ * ascending (room for m); rows[n_checked*k] = one coefficient row per
+ * checked chunk over the survivors, taken from the decode-plan composition
+ * of the survivors-only mask. Returns n_checked or -errno as above (outputs
+ * are then left unwritten); w=8 matrix techniques only, the others return
+ * ECX_ERR_INVAL. */
+ECX_API int ecx_verify_plan_probe(int technique, int k, int m,
+                                  uint64_t present_mask, int *survivors,
+                                  int *checked, uint8_t *rows);
+
 /* CPU-only (no GPU context): what the bitmatrix launcher (cauchy_orig,
  * cauchy_good) would launch for n_out outputs over n_src sources of
  * chunk_bytes each, at word size w and packet size pkt, when the rows have
@@ -373,6 +416,15 @@ ECX_API int ecx_encode_chunks_host(ecx_ctx *ctx,
  * buffers at ErasureCodeIsa.cc:212-226). */
 ECX_API int ecx_decode_chunks_host(ecx_ctx *ctx, uint8_t *const *chunks,
                                    uint64_t present_mask, size_t chunk_bytes);
+
+/* ecx_verify_batch for a scrub caller with one stripe in host memory:
+ * chunks[] has k+m entries, entries of absent ids are ignored, *bad receives
+ * the stripe's word. A NULL entry for a present id is ECX_ERR_INVAL — unlike
+ * decode, a chunk that is not given cannot be vouched for. Uploads the
+ * present chunks, downloads 8 bytes; same refusals as the batch call. */
+ECX_API int ecx_verify_chunks_host(ecx_ctx *ctx, const uint8_t *const *chunks,
+                                   uint64_t present_mask, size_t chunk_bytes,
+                                   uint64_t *bad);
 
 ECX_API int ecx_encode_delta_host(ecx_ctx *ctx, const uint8_t *old_data,
                                   const uint8_t *new_data, uint8_t *delta,
