@@ -121,6 +121,19 @@ def _lib():
     lib.ecx_verify_chunks_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_uint64, ctypes.c_size_t,
                                            ctypes.POINTER(ctypes.c_uint64)]
+    lib.ecx_crc32c_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_long, ctypes.c_size_t,
+                                     ctypes.c_uint64, ctypes.c_void_p,
+                                     ctypes.c_int, ctypes.c_void_p,
+                                     ctypes.c_int]
+    lib.ecx_crc32c_probe.argtypes = [ctypes.c_uint32, ctypes.c_void_p,
+                                     ctypes.c_size_t,
+                                     ctypes.POINTER(ctypes.c_uint32)]
+    lib.ecx_crc32c_shift_probe.argtypes = [ctypes.c_uint32, ctypes.c_uint64,
+                                           ctypes.POINTER(ctypes.c_uint32)]
+    lib.ecx_crc32c_plan_probe.argtypes = [ctypes.c_size_t, ctypes.c_long,
+                                          ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_long)]
     lib.ecx_bitmatrix_plan_probe.argtypes = [
         ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_size_t,
@@ -290,6 +303,45 @@ def verify_plan_probe(technique, k, m, present_mask):
         ck.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
         rows.ctypes.data_as(ctypes.c_void_p)), "ecx_verify_plan_probe")
     return sv[:k], ck[:n], rows.reshape(-1)[:n * k].reshape(n, k)
+
+
+def crc32c_probe(seed, data, with_path=False):
+    """CPU-only: ceph_crc32c(seed, data) by the library's host routine (no
+    inversion of seed or result). data is bytes or a uint8 array (any
+    offset, contiguous). with_path=True returns (crc, path), path "sse4.2"
+    or "tables"."""
+    a = np.frombuffer(data, dtype=np.uint8) if isinstance(
+        data, (bytes, bytearray, memoryview)) else np.asarray(data)
+    if a.dtype != np.uint8 or a.ndim != 1 or (a.size and a.strides[0] != 1):
+        raise EcError("ecx_crc32c_probe: need contiguous uint8 data")
+    out = ctypes.c_uint32()
+    r = _ck(lib().ecx_crc32c_probe(
+        int(seed) & 0xFFFFFFFF, a.ctypes.data if a.size else None, a.size,
+        ctypes.byref(out)), "ecx_crc32c_probe")
+    return (out.value, "sse4.2" if r else "tables") if with_path else out.value
+
+
+def crc32c_shift_probe(crc, nbytes):
+    """CPU-only: crc * x^(8*nbytes) mod P, the CRC state after nbytes zero
+    bytes: f(seed, A+B) == shift(f(seed, A), len(B)) ^ f(0, B)."""
+    out = ctypes.c_uint32()
+    _ck(lib().ecx_crc32c_shift_probe(int(crc) & 0xFFFFFFFF, nbytes,
+                                     ctypes.byref(out)),
+        "ecx_crc32c_shift_probe")
+    return out.value
+
+
+_CRC_PLAN_FIELDS = ("seg_bytes", "segs_per_block", "blocks_per_chunk", "grid",
+                    "threads", "lds_bytes", "launches", "reserved")
+
+
+def crc32c_plan_probe(chunk_bytes, n_stripes, n_chunks):
+    """CPU-only: what crc32c_batch would launch for n_chunks masked chunks,
+    as a dict. Segments and blocks are aligned to the END of a chunk."""
+    out = (ctypes.c_long * 8)()
+    _ck(lib().ecx_crc32c_plan_probe(chunk_bytes, n_stripes, n_chunks, out),
+        "ecx_crc32c_plan_probe")
+    return dict(zip(_CRC_PLAN_FIELDS, (int(v) for v in out)))
 
 
 _BIT_KNOBS = (("ECX_BITQ", 16), ("ECX_BITW", 8), ("ECX_BITREG", 2),
@@ -487,6 +539,44 @@ class EcContext:
         finally:
             if own:
                 self.dbuf_free(d_bad)
+        return words
+
+    def crc32c_batch(self, dptr, n_stripes, chunk_bytes, chunk_mask=None,
+                     seeds=None, chain=False, d_crc=None, slot=0):
+        """ceph_crc32c of every chunk of a batch in chunk_mask (None = all
+        k+m), as an (n_stripes, k+m) uint32 array. seeds: None (0xFFFFFFFF),
+        a numpy array uploaded for the call, or a device pointer — one word
+        per output word, or k+m words when chain. chain=True: row s is the
+        hash of each shard's chunks of stripes 0..s concatenated. d_crc None
+        = a temporary zeroed device array (unmasked columns come back 0);
+        otherwise a device array of n_stripes*(k+m) words, whose unmasked
+        words are kept. The batch is only read."""
+        n = self.k + self.m
+        if chunk_mask is None:
+            chunk_mask = (1 << n) - 1
+        words = np.zeros((max(int(n_stripes), 0), n), dtype=np.uint32)
+        temps = []
+        try:
+            if d_crc is None:
+                d_crc = self.dbuf_alloc(max(words.nbytes, 4))
+                temps.append(d_crc)
+                self.upload(d_crc, words, slot)
+            if isinstance(seeds, np.ndarray):
+                want = n if chain else words.size
+                h = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+                if h.size != want:
+                    raise EcError(f"ecx_crc32c_batch: need {want} seeds, "
+                                  f"got {h.size}")
+                seeds = self.dbuf_alloc(max(h.nbytes, 4))
+                temps.append(seeds)
+                self.upload(seeds, h, slot)
+            _ck(lib().ecx_crc32c_batch(self._h, dptr, n_stripes, chunk_bytes,
+                                       chunk_mask, seeds, int(bool(chain)),
+                                       d_crc, slot), "ecx_crc32c_batch")
+            self.download(words, d_crc, slot)
+        finally:
+            for p in temps:
+                self.dbuf_free(p)
         return words
 
     def matmul_batch(self, dptr, n_stripes, chunk_bytes, src_ids, out_ids,

@@ -51,6 +51,7 @@
 #include "decode_multi.h"
 #include "update_plan.h"
 #include "verify_plan.h"
+#include "crc_plan.h"
 #include "bit_plan.h"
 #include "stream_walk.h"
 
@@ -1191,6 +1192,171 @@ __global__ __launch_bounds__(256) void ec_fill_random_kernel(
   for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < n_words;
        p += (long)gridDim.x * blockDim.x)
     out[p] = ecx_splitmix64(seed ^ (uint64_t)p);
+}
+
+// ---------------------------------------------------------------------------
+// Per-shard CRC-32C (ecx_crc32c_batch; constants and the
+// end-aligned tiling: crc_plan.h)
+// ---------------------------------------------------------------------------
+__constant__ ecx::CrcTables ecx_crc_tab{};
+__constant__ ecx::CrcCombine ecx_crc_comb{};
+
+constexpr int ECX_CRC_CHAIN_T = 1024;  // lanes of the chain scan
+static_assert(ECX_CRC_CHAIN_T == 1 << ecx::CRC_CHAIN_LOG2, "chain plan split");
+
+// What the three CRC kernels share about a call.
+struct EcCrcArgs {
+  uint32_t ids[64];      // chunk id of the j-th masked chunk
+  uint32_t n_ids;        // masked chunks per stripe
+  uint32_t n_chunks;     // k + m
+  uint32_t bpc;          // blocks per chunk
+  uint32_t x_chunk;      // x^(8 * chunk_bytes)
+  uint64_t chunk_bytes;
+};
+
+// a * b mod P, branch-free (ecx::crc_mulmod is the readable form)
+__device__ __forceinline__ uint32_t ecx_crc_mul(uint32_t a, uint32_t b) {
+  uint32_t r = 0;
+#pragma unroll
+  for (int i = 0; i < 32; i++) {
+    r ^= a & (uint32_t)((int32_t)(b << i) >> 31);
+    a = (a >> 1) ^ (ecx::CRC32C_POLY & (0u - (a & 1)));
+  }
+  return r;
+}
+
+// First launch: every masked word becomes the term its seed contributes,
+// shift(seed, chunk_bytes) — or 0 in chain mode, where the scan brings the
+// seed in. d_seed may be d_crc itself (each word is read, then written, by
+// one lane).
+template <int = 0>
+__global__ __launch_bounds__(256) void ec_crc32c_seed_kernel(
+    const uint32_t* d_seed, uint32_t* d_crc, EcCrcArgs a, uint32_t n_words,
+    int chain) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_words) return;
+  const size_t w = (size_t)(i / a.n_ids) * a.n_chunks + a.ids[i % a.n_ids];
+  uint32_t v = 0;
+  if (!chain) v = ecx_crc_mul(d_seed ? d_seed[w] : 0xFFFFFFFFu, a.x_chunk);
+  d_crc[w] = v;
+}
+
+// One block = CRC_BLOCK_BYTES of one chunk, counted from the chunk's END
+// (the first block of a chunk may start before byte 0; what lies there is
+// skipped, leading zeros do not move a zero state). Coalesced 16-byte loads
+// into an LDS image with one padded row per lane; each lane then hashes its
+// own CRC_SEG_BYTES from state 0 by slice-by-4 lookups in LDS tables,
+// multiplies by x^(8 * bytes that follow it in the block), the block XORs
+// its lanes together, multiplies by x^(8 * bytes that follow the block) and
+// XORs the result into the chunk's word. XOR commutes, so the word does not
+// depend on the order in which a chunk's blocks arrive.
+template <bool NT>
+__global__ __launch_bounds__(ecx::CRC_THREADS) void ec_crc32c_kernel(
+    const uint8_t* __restrict__ buf, uint32_t* d_crc, EcCrcArgs a) {
+  constexpr int L = ecx::CRC_SEG_BYTES, T = ecx::CRC_THREADS;
+  constexpr int STRIDE = ecx::CRC_SEG_STRIDE, NV = L / 16;
+  __shared__ __attribute__((aligned(16))) uint8_t lds[ecx::CRC_LDS_BYTES];
+  uint32_t* s_tab = reinterpret_cast<uint32_t*>(lds + STRIDE * T);
+  // the waves' totals go into the pad of row 0, which staging never writes:
+  // one more LDS object would cost the fourth block per CU
+  uint32_t* s_red = reinterpret_cast<uint32_t*>(lds + L);
+  static_assert(T / 64 * 4 <= STRIDE - L, "wave totals fit the row pad");
+  const uint32_t t = threadIdx.x;
+  const uint32_t b = blockIdx.x % a.bpc, cj = blockIdx.x / a.bpc;
+  const uint32_t stripe = cj / a.n_ids, chunk = a.ids[cj % a.n_ids];
+  const size_t word = (size_t)stripe * a.n_chunks + chunk;
+  const uint8_t* src = buf + word * a.chunk_bytes;
+  // offset in the chunk of this block's first byte; < 0 only for b == 0
+  const int64_t base = (int64_t)(b + 1) * ecx::CRC_BLOCK_BYTES -
+                       (int64_t)a.bpc * ecx::CRC_BLOCK_BYTES +
+                       (int64_t)a.chunk_bytes - ecx::CRC_BLOCK_BYTES;
+
+#pragma unroll
+  for (int q = 0; q < 4; q++)
+    s_tab[t + T * q] = (&ecx_crc_tab.t[0][0])[t + T * q];
+  // items before byte 0 load byte 0's vector instead and are never read
+#pragma unroll
+  for (int j = 0; j < NV; j++) {
+    const uint32_t i = t + T * j;
+    const int64_t off = base + (int64_t)i * 16;
+    const v4u d = ecx_ld16<NT>(src + (off < 0 ? 0 : off));
+    *reinterpret_cast<v4u*>(lds + (i / NV) * STRIDE + (i % NV) * 16) = d;
+  }
+  __syncthreads();
+
+  const int64_t seg0 = base + (int64_t)t * L;
+  const int first = seg0 >= 0 ? 0 : (int)((-seg0 > L ? L : -seg0) / 16);
+  uint32_t crc = 0;
+#pragma unroll
+  for (int q = 0; q < NV; q++) {
+    if (q < first) continue;
+    const v4u d = *reinterpret_cast<const v4u*>(lds + t * STRIDE + q * 16);
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      const uint32_t x = crc ^ d[e];
+      crc = s_tab[768 + (x & 255)] ^ s_tab[512 + ((x >> 8) & 255)] ^
+            s_tab[256 + ((x >> 16) & 255)] ^ s_tab[x >> 24];
+    }
+  }
+
+  uint32_t v = ecx_crc_mul(crc, ecx_crc_comb.seg[t]);
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v ^= __shfl_xor(v, o);
+  if ((t & 63) == 0) s_red[t >> 6] = v;
+  __syncthreads();
+  if (t == 0) {
+    v = s_red[0] ^ s_red[1] ^ s_red[2] ^ s_red[3];
+    uint32_t after = a.bpc - 1 - b;  // blocks that follow in the chunk
+    for (int i = 0; after; after >>= 1, i++)
+      if (after & 1) v = ecx_crc_mul(v, ecx_crc_comb.blk[i]);
+    atomicXor(&d_crc[word], v);
+  }
+}
+static_assert(ecx::CRC_THREADS == 256, "s_red sum and table fill assume 256");
+
+// Chain mode, after the hash pass: d_crc[s][c] holds f(0, chunk c of stripe
+// s); make it the hash of stripes 0..s of shard c concatenated, from the
+// shard's seed. One block per masked shard. Lane t owns `run` consecutive
+// stripes and folds them in order; the lanes' totals go through a log-step
+// scan in LDS with the constants x^(8C * run * 2^i); each lane then adds what
+// precedes its run, advanced by one chunk per stripe.
+template <int = 0>
+__global__ __launch_bounds__(ECX_CRC_CHAIN_T) void ec_crc32c_chain_kernel(
+    const uint32_t* __restrict__ d_seed, uint32_t* __restrict__ d_crc,
+    EcCrcArgs a, ecx::CrcChainPlan cp, uint32_t n_stripes) {
+  __shared__ uint32_t s_tot[ECX_CRC_CHAIN_T];
+  const uint32_t t = threadIdx.x, c = a.ids[blockIdx.x];
+  const uint32_t s0 = min(t * cp.run, n_stripes);
+  const uint32_t s1 = min(s0 + cp.run, n_stripes);
+  uint32_t* col = d_crc + c;
+  uint32_t acc = t == 0 ? (d_seed ? d_seed[c] : 0xFFFFFFFFu) : 0;
+  for (uint32_t s = s0; s < s1; s += 8) {
+    uint32_t h[8];
+#pragma unroll
+    for (int e = 0; e < 8; e++)
+      h[e] = s + e < s1 ? col[(size_t)(s + e) * a.n_chunks] : 0;
+#pragma unroll
+    for (int e = 0; e < 8; e++)
+      if (s + e < s1) {
+        acc = ecx_crc_mul(acc, a.x_chunk) ^ h[e];
+        col[(size_t)(s + e) * a.n_chunks] = acc;
+      }
+  }
+  s_tot[t] = acc;
+  __syncthreads();
+#pragma unroll 1
+  for (int i = 0; i < ecx::CRC_CHAIN_LOG2; i++) {
+    const uint32_t d = 1u << i;
+    const uint32_t up = t >= d ? ecx_crc_mul(s_tot[t - d], cp.x_step[i]) : 0;
+    __syncthreads();
+    s_tot[t] ^= up;
+    __syncthreads();
+  }
+  uint32_t carry = t ? s_tot[t - 1] : 0;
+  for (uint32_t s = s0; s < s1; s++) {
+    carry = ecx_crc_mul(carry, a.x_chunk);
+    col[(size_t)s * a.n_chunks] ^= carry;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -3865,6 +4031,109 @@ int ecx_apply_deltas_host(ecx_ctx* ctx, const uint8_t* const* deltas,
     HIP_TRY(hipMemcpyAsync(parities[j], s.d_stage + (size_t)out_ids[j] * bytes,
                            bytes, hipMemcpyDeviceToHost, s.stream));
   HIP_TRY(wait_stream(s.stream));
+  return ECX_OK;
+}
+
+}  // extern "C"
+
+// ---- per-shard CRC-32C: host side ----
+// Kept at the end of the file, and every CRC kernel a template: kernels are
+// emitted where they are first used, so the code of every other kernel
+// stays at the offset it had before these existed.
+// Seed pass, hash pass and (chain mode) the scan, back to back under one
+// event pair. Arguments are validated and the slot is locked by the caller.
+static int run_crc(ecx_ctx* ctx, Slot& s, const uint8_t* d_buf,
+                   long n_stripes, const EcCrcArgs& a, const ecx::CrcPlan& p,
+                   const uint32_t* d_seed, int chain, uint32_t* d_crc) {
+  const uint32_t n_words = (uint32_t)n_stripes * a.n_ids;
+  ecx::CrcChainPlan cp;
+  if (chain) ecx::plan_crc_chain(a.chunk_bytes, n_stripes, cp);
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(timer_start(s));
+  hipLaunchKernelGGL(ec_crc32c_seed_kernel<>, dim3((n_words + 255) / 256),
+                     dim3(256), 0, s.stream, d_seed, d_crc, a, n_words, chain);
+  HIP_TRY(hipGetLastError());
+  if (env_nt())
+    hipLaunchKernelGGL(ec_crc32c_kernel<true>, dim3((unsigned)p.grid),
+                       dim3(ecx::CRC_THREADS), 0, s.stream, d_buf, d_crc, a);
+  else
+    hipLaunchKernelGGL(ec_crc32c_kernel<false>, dim3((unsigned)p.grid),
+                       dim3(ecx::CRC_THREADS), 0, s.stream, d_buf, d_crc, a);
+  HIP_TRY(hipGetLastError());
+  if (chain) {
+    hipLaunchKernelGGL(ec_crc32c_chain_kernel<>, dim3(a.n_ids),
+                       dim3(ECX_CRC_CHAIN_T), 0, s.stream, d_seed, d_crc, a,
+                       cp, (uint32_t)n_stripes);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(timer_stop(s));
+  return ECX_OK;
+}
+
+extern "C" {
+
+int ecx_crc32c_batch(ecx_ctx* ctx, const void* dptr, long n_stripes,
+                     size_t chunk_bytes, uint64_t chunk_mask,
+                     const uint32_t* d_seed, int chain, uint32_t* d_crc,
+                     int slot) {
+  if (!ctx || !dptr || !d_crc || slot < 0 || slot >= (int)ctx->slots.size())
+    return ECX_ERR_INVAL;
+  const int n = ctx->k + ctx->m;
+  if (n < 64 && (chunk_mask >> n)) return ECX_ERR_INVAL;
+  EcCrcArgs a = {};
+  for (int c = 0; c < n; c++)
+    if (chunk_mask >> c & 1) a.ids[a.n_ids++] = (uint32_t)c;
+  // sizes are judged as for a full mask, so a refusal does not depend on it
+  ecx::CrcPlan p;
+  if (!ecx::plan_crc(chunk_bytes, n_stripes, n, p)) return ECX_ERR_INVAL;
+  if (((uintptr_t)d_crc | (uintptr_t)d_seed) & 3) return ECX_ERR_INVAL;
+  // the words are written while the batch is read, and seeds are read while
+  // words are written: no overlap, but for the in-place append
+  const uintptr_t b0 = (uintptr_t)dptr, w0 = (uintptr_t)d_crc,
+                  s0 = (uintptr_t)d_seed;
+  const uintptr_t b1 = b0 + (uintptr_t)n_stripes * n * chunk_bytes;
+  const uintptr_t w1 = w0 + (uintptr_t)n_stripes * n * 4;
+  const uintptr_t s1 = s0 + (uintptr_t)(chain ? 1 : n_stripes) * n * 4;
+  if (w0 < b1 && b0 < w1) return ECX_ERR_INVAL;
+  if (d_seed) {
+    if (s0 < b1 && b0 < s1) return ECX_ERR_INVAL;
+    if (s0 < w1 && w0 < s1 && !(s0 == w0 && !chain)) return ECX_ERR_INVAL;
+  }
+  if (a.n_ids == 0) return ECX_OK;  // nothing to hash, nothing launched
+  ecx::plan_crc(chunk_bytes, n_stripes, (int)a.n_ids, p);
+  a.n_chunks = (uint32_t)n;
+  a.bpc = (uint32_t)p.blocks_per_chunk;
+  a.chunk_bytes = chunk_bytes;
+  a.x_chunk = ecx::crc_xpow8(chunk_bytes);
+  Slot& s = ctx->slots[slot];
+  std::lock_guard<std::recursive_mutex> g(s.mu);
+  return run_crc(ctx, s, (const uint8_t*)dptr, n_stripes, a, p, d_seed, chain,
+                 d_crc);
+}
+
+int ecx_crc32c_probe(uint32_t seed, const void* data, size_t len,
+                     uint32_t* out) {
+  if (!out || (!data && len)) return ECX_ERR_INVAL;
+  int path = 0;
+  *out = ecx::crc32c_host(seed, data, len, &path);
+  return path;
+}
+
+int ecx_crc32c_shift_probe(uint32_t crc, uint64_t nbytes, uint32_t* out) {
+  if (!out) return ECX_ERR_INVAL;
+  *out = ecx::crc32c_shift(crc, nbytes);
+  return ECX_OK;
+}
+
+int ecx_crc32c_plan_probe(size_t chunk_bytes, long n_stripes, int n_chunks,
+                          long out[8]) {
+  ecx::CrcPlan p;
+  if (!out || !ecx::plan_crc(chunk_bytes, n_stripes, n_chunks, p))
+    return ECX_ERR_INVAL;
+  const long v[8] = {p.seg_bytes, p.segs_per_block, p.blocks_per_chunk,
+                     p.grid,      p.threads,        p.lds_bytes,
+                     p.launches,  0};
+  std::copy(v, v + 8, out);
   return ECX_OK;
 }
 

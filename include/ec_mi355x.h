@@ -23,6 +23,9 @@
  *   scrub's re-encode-and-compare (encode_chunks     src/erasure-code/ErasureCodeInterface.h
  *     into a second buffer, then a compare pass)       encode_chunks, as used by the OSD
  *     -> ecx_verify_batch()                            scrub path
+ *   ceph_crc32c over each shard                      src/osd/ECUtil.cc
+ *     (ECUtil::HashInfo::append, EC deep scrub)        HashInfo::append
+ *     -> ecx_crc32c_batch()
  *   minimum_to_decode survivor choice                src/erasure-code/ErasureCode.cc:154-170
  *     -> ecx_minimum_to_decode()
  *   get_chunk_size / get_alignment                   ErasureCodeIsa.cc:65-79,
@@ -309,6 +312,67 @@ ECX_API int ecx_verify_batch(ecx_ctx *ctx, const void *dptr, long n_stripes,
 ECX_API int ecx_verify_plan_probe(int technique, int k, int m,
                                   uint64_t present_mask, int *survivors,
                                   int *checked, uint8_t *rows);
+
+/* ---------------- per-shard CRC-32C ----------------------------------------
+ * The hash the OSD keeps per shard: ECUtil::HashInfo::append runs
+ * ceph_crc32c(old_hash, shard_bytes, len) over each of the k+m shards of a
+ * write (cumulative hashes start at -1), and EC deep scrub hashes each stored
+ * shard again and compares. f(seed, data, len) = ceph_crc32c: the Castagnoli
+ * polynomial, reflected (0x82F63B78), NO inversion of the seed or of the
+ * result (the standard CRC-32C of a buffer is ~f(~0, buf)). The hash does
+ * not depend on the code: every technique and w is accepted.
+ *
+ * dptr is the standard batch buffer. d_crc is a device array of
+ * n_stripes*(k+m) 32-bit words; the word of chunk c of stripe s is
+ * d_crc[s*(k+m)+c]. Exactly the words of the chunks in chunk_mask are
+ * written, all others are left as they were.
+ *   chain == 0: every chunk is hashed on its own. d_seed NULL seeds every
+ *     hash with 0xFFFFFFFF; otherwise d_seed has the layout of d_crc, one
+ *     seed per word. d_seed == d_crc is allowed: "append one more chunk to
+ *     each running hash", in place.
+ *   chain != 0: the stripes are consecutive stripes of one object (a
+ *     HashInfo append of a multi-stripe write). d_seed is NULL or k+m words,
+ *     one per shard; d_crc[s][c] = the hash of shard c's chunks of stripes
+ *     0..s concatenated, from that shard's seed, so row n_stripes-1 is the
+ *     new cumulative_shard_hashes.
+ * The batch is never written. Two launches whatever the mask (a seed pass
+ * over the words, then the hash pass), a third in chain mode (a log-step
+ * scan over the words, not a loop over stripes); ecx_last_kernel_ms covers
+ * the whole call, first launch to last. All validation precedes any GPU
+ * work and a refused call writes nothing: ECX_ERR_INVAL for a NULL ctx, dptr
+ * or d_crc, a bad slot, chunk_bytes 0 or not a multiple of 16, n_stripes
+ * outside 1..65535, d_crc or d_seed not 4-byte aligned, a d_crc or d_seed
+ * range that intersects the batch, a d_seed range that overlaps d_crc (other
+ * than d_seed == d_crc with chain == 0), a mask bit at position k+m or
+ * above, or a shape whose n_stripes*(k+m)*ceil(chunk_bytes/32768) blocks do
+ * not fit 31 bits. A mask of 0 returns ECX_OK with nothing launched. There
+ * is no host-pointer form: a chunk in host memory is hashed faster by the
+ * host's own crc32 instruction than PCIe can deliver it. */
+ECX_API int ecx_crc32c_batch(ecx_ctx *ctx, const void *dptr, long n_stripes,
+                             size_t chunk_bytes, uint64_t chunk_mask,
+                             const uint32_t *d_seed, int chain,
+                             uint32_t *d_crc, int slot);
+/* CPU-only (no GPU context). The library's host implementation of f: the
+ * SSE4.2 crc32 instruction where the CPU has it, slice-by-4 tables
+ * otherwise. *out = f(seed, data, len); returns 1 when the instruction was
+ * used, 0 for the tables, ECX_ERR_INVAL for a NULL out (or NULL data with
+ * len > 0). */
+ECX_API int ecx_crc32c_probe(uint32_t seed, const void *data, size_t len,
+                             uint32_t *out);
+/* CPU-only. *out = crc * x^(8*nbytes) mod P: the state after nbytes zero
+ * bytes. The one host routine the kernel's combine constants come from;
+ * f(seed, A||B) = shift(f(seed, A), |B|) ^ f(0, B). */
+ECX_API int ecx_crc32c_shift_probe(uint32_t crc, uint64_t nbytes,
+                                   uint32_t *out);
+/* CPU-only: what the launcher would launch for n_chunks masked chunks of
+ * chunk_bytes in each of n_stripes stripes. out[0..7] = bytes per lane
+ * segment L, segments per block, blocks per chunk, grid, threads, LDS bytes,
+ * launches (chain mode adds one), 0. Segments and blocks are aligned to the
+ * END of the chunk: segment j from the end is [C-(j+1)L, C-jL) cut at 0, a
+ * block is `segments per block` of them. ECX_ERR_INVAL as the launcher for
+ * bad sizes, n_chunks outside 1..64 or a NULL out. */
+ECX_API int ecx_crc32c_plan_probe(size_t chunk_bytes, long n_stripes,
+                                  int n_chunks, long out[8]);
 
 /* CPU-only (no GPU context): what the bitmatrix launcher (cauchy_orig,
  * cauchy_good) would launch for n_out outputs over n_src sources of
