@@ -121,6 +121,28 @@ def _lib():
     lib.ecx_verify_chunks_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_uint64, ctypes.c_size_t,
                                            ctypes.POINTER(ctypes.c_uint64)]
+    lib.ecx_locate_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_long, ctypes.c_size_t,
+                                     ctypes.c_uint64, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_int]
+    lib.ecx_locate_chunks_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_uint64, ctypes.c_size_t,
+                                           ctypes.POINTER(ctypes.c_uint64),
+                                           ctypes.POINTER(ctypes.c_uint64)]
+    lib.ecx_locate_plan_probe.argtypes = [
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+        ctypes.c_void_p]
+    lib.ecx_locate_word_probe.restype = ctypes.c_uint64
+    lib.ecx_locate_word_probe.argtypes = [ctypes.c_uint64] * 4
+    lib.ecx_repair_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_long, ctypes.c_size_t,
+                                     ctypes.c_uint64, ctypes.c_void_p,
+                                     ctypes.c_void_p,
+                                     ctypes.POINTER(ctypes.c_long),
+                                     ctypes.POINTER(ctypes.c_long),
+                                     ctypes.c_int]
     lib.ecx_crc32c_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_long, ctypes.c_size_t,
                                      ctypes.c_uint64, ctypes.c_void_p,
@@ -303,6 +325,37 @@ def verify_plan_probe(technique, k, m, present_mask):
         ck.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
         rows.ctypes.data_as(ctypes.c_void_p)), "ecx_verify_plan_probe")
     return sv[:k], ck[:n], rows.reshape(-1)[:n * k].reshape(n, k)
+
+
+def locate_plan_probe(technique, k, m, present_mask):
+    """CPU-only: how locate_batch would plan this present mask. Returns
+    (survivors, checked, cand_survivors, cand_checked, cand_rows): the base
+    plan as verify_plan_probe gives it, and for candidate i (survivor i left
+    out) its k survivors, the n_checked - 1 chunks it checks and one row per
+    such chunk over its survivors; shapes (k, k), (k, n-1) and (k, n-1, k)."""
+    t = TECHNIQUES[technique] if isinstance(technique, str) else technique
+    k1, m1 = max(k, 1), max(m, 1)
+    ip = ctypes.POINTER(ctypes.c_int)
+    sv = np.zeros(k1, dtype=np.int32)
+    ck = np.zeros(m1, dtype=np.int32)
+    csv = np.zeros(k1 * k1, dtype=np.int32)
+    cck = np.zeros(k1 * m1, dtype=np.int32)
+    rows = np.zeros(k1 * m1 * k1, dtype=np.uint8)
+    n = _ck(lib().ecx_locate_plan_probe(
+        t, k, m, present_mask, sv.ctypes.data_as(ip), ck.ctypes.data_as(ip),
+        csv.ctypes.data_as(ip), cck.ctypes.data_as(ip),
+        rows.ctypes.data_as(ctypes.c_void_p)), "ecx_locate_plan_probe")
+    return (sv[:k], ck[:n], csv.reshape(k, k),
+            cck[:k * (n - 1)].reshape(k, n - 1),
+            rows[:k * (n - 1) * k].reshape(k, n - 1, k))
+
+
+def locate_word_probe(present_mask, survivor_mask, bad, refuted):
+    """CPU-only: the culprit word locate_batch forms for one stripe from its
+    verify word and the survivor candidates that were refuted."""
+    return int(lib().ecx_locate_word_probe(int(present_mask),
+                                           int(survivor_mask), int(bad),
+                                           int(refuted)))
 
 
 def crc32c_probe(seed, data, with_path=False):
@@ -541,6 +594,64 @@ class EcContext:
                 self.dbuf_free(d_bad)
         return words
 
+    def _locate_call(self, n_stripes, present_mask, d_bad, d_culprit, slot,
+                     call):
+        """Shared by locate_batch and repair_batch: default mask, temporary
+        device arrays where none are given, call(mask, d_bad, d_culprit),
+        then both arrays downloaded."""
+        if present_mask is None:
+            present_mask = (1 << (self.k + self.m)) - 1
+        n = max(int(n_stripes), 0)
+        bad = np.zeros(n, dtype=np.uint64)
+        culprit = np.zeros(n, dtype=np.uint64)
+        temps = []
+        try:
+            if d_bad is None:
+                d_bad = self.dbuf_alloc(max(bad.nbytes, 8))
+                temps.append(d_bad)
+            if d_culprit is None:
+                d_culprit = self.dbuf_alloc(max(culprit.nbytes, 8))
+                temps.append(d_culprit)
+            out = call(present_mask, d_bad, d_culprit)
+            self.download(bad, d_bad, slot)
+            self.download(culprit, d_culprit, slot)
+        finally:
+            for p in temps:
+                self.dbuf_free(p)
+        return bad, culprit, out
+
+    def locate_batch(self, dptr, n_stripes, chunk_bytes, present_mask=None,
+                     d_bad=None, d_culprit=None, slot=0):
+        """verify_batch plus the culprit: returns (bad, culprit), two uint64
+        arrays of n_stripes words. bad is verify_batch's result; bit x of
+        culprit[s] is set when leaving present chunk x out makes the rest of
+        stripe s consistent. Clean stripe: culprit == present_mask; one
+        damaged chunk x: 1 << x; not locatable: 0. Needs at least k + 2
+        present chunks. The batch is only read."""
+        def call(mask, db, dc):
+            _ck(lib().ecx_locate_batch(self._h, dptr, n_stripes, chunk_bytes,
+                                       mask, db, dc, slot),
+                "ecx_locate_batch")
+        return self._locate_call(n_stripes, present_mask, d_bad, d_culprit,
+                                 slot, call)[:2]
+
+    def repair_batch(self, dptr, n_stripes, chunk_bytes, present_mask=None,
+                     d_bad=None, d_culprit=None, slot=0):
+        """locate_batch, then every stripe whose culprit is a single chunk
+        gets that chunk (and its absent chunks) rebuilt in place; all other
+        stripes are not written. Returns (bad, culprit, n_repaired,
+        n_unlocatable) — the words describe the batch before the repair."""
+        def call(mask, db, dc):
+            rep, unl = ctypes.c_long(), ctypes.c_long()
+            _ck(lib().ecx_repair_batch(self._h, dptr, n_stripes, chunk_bytes,
+                                       mask, db, dc, ctypes.byref(rep),
+                                       ctypes.byref(unl), slot),
+                "ecx_repair_batch")
+            return rep.value, unl.value
+        bad, culprit, (rep, unl) = self._locate_call(
+            n_stripes, present_mask, d_bad, d_culprit, slot, call)
+        return bad, culprit, rep, unl
+
     def crc32c_batch(self, dptr, n_stripes, chunk_bytes, chunk_mask=None,
                      seeds=None, chain=False, d_crc=None, slot=0):
         """ceph_crc32c of every chunk of a batch in chunk_mask (None = all
@@ -663,6 +774,27 @@ class EcContext:
             sizes.pop() if sizes else 0, ctypes.byref(word)),
             "ecx_verify_chunks_host")
         return word.value
+
+    def locate_chunks(self, chunks, present=None):
+        """locate_batch for one stripe in host memory, arguments as
+        verify_chunks. Returns (bad, culprit) as ints."""
+        if present is None:
+            present = [True] * (self.k + self.m)
+        mask = 0
+        for i, p in enumerate(present):
+            if p:
+                mask |= 1 << i
+        sizes = {c.nbytes for c, p in zip(chunks, present)
+                 if p and c is not None}
+        if len(sizes) > 1:
+            raise EcError("ecx_locate_chunks_host: equal-length chunks "
+                          f"required, got sizes {sorted(sizes)}")
+        bad, culprit = ctypes.c_uint64(), ctypes.c_uint64()
+        _ck(lib().ecx_locate_chunks_host(
+            self._h, _ptr_array(list(chunks)), mask,
+            sizes.pop() if sizes else 0, ctypes.byref(bad),
+            ctypes.byref(culprit)), "ecx_locate_chunks_host")
+        return bad.value, culprit.value
 
     def encode_delta(self, old, new):
         delta = np.zeros_like(old)

@@ -51,6 +51,7 @@
 #include "decode_multi.h"
 #include "update_plan.h"
 #include "verify_plan.h"
+#include "locate_plan.h"
 #include "crc_plan.h"
 #include "bit_plan.h"
 #include "stream_walk.h"
@@ -1360,6 +1361,119 @@ __global__ __launch_bounds__(ECX_CRC_CHAIN_T) void ec_crc32c_chain_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Locating the corrupt chunk (ecx_locate_batch). Templates,
+// launched from the end of the file like the CRC kernels.
+// ---------------------------------------------------------------------------
+
+#define ECX_LOCATE_LIST_T 1024
+
+// The stripes ec_gf_verify_kernel flagged, as a list: list[0] = how many,
+// list[1..] = their indices in no particular order. One block: the count is
+// formed in LDS and written once, so the list needs no clearing and a clean
+// batch costs one pass over n_stripes words. A wave reserves its entries
+// with one LDS atomic.
+template <int = 0>
+__global__ __launch_bounds__(ECX_LOCATE_LIST_T) void ec_locate_list_kernel(
+    const unsigned long long* __restrict__ bad, uint32_t* __restrict__ list,
+    uint32_t n_stripes) {
+  __shared__ uint32_t s_count;
+  if (threadIdx.x == 0) s_count = 0;
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63u;
+  // whole waves stay in the loop together: the ballot needs every lane
+  for (uint32_t s0 = threadIdx.x - lane; s0 < n_stripes;
+       s0 += ECX_LOCATE_LIST_T) {
+    const uint32_t s = s0 + lane;
+    const bool flagged = s < n_stripes && bad[s] != 0ull;
+    const unsigned long long vote = __ballot(flagged);
+    if (vote == 0ull) continue;
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(&s_count, (uint32_t)__popcll(vote));
+    base = __shfl(base, 0);
+    if (flagged)
+      list[1 + base + (uint32_t)__popcll(vote & ((1ull << lane) - 1ull))] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) list[0] = s_count;
+}
+
+// One candidate "survivor cand is the damaged one", checked on the flagged
+// stripes only: the verify computation (sources = the candidate's survivors,
+// outputs = its checked chunks) over tiles numbered
+//     (index into the flagged list, tile in chunk)
+// with the tile fastest. The count of flagged stripes is known only on the
+// device, so the grid is sized by the host for residency and strides over
+// count x tpc; the step is split on the host into (list entries, tiles) so
+// the device adds and carries. With nothing flagged a block leaves after one
+// scalar load. A wave in which any lane differs in any output sets bit cand
+// of the stripe's refuted word with one atomicOr from one lane.
+template <int NOUT>
+__global__ __launch_bounds__(256, NOUT < 4 ? 8 : 6) void ec_gf_locate_kernel(
+    const uint8_t* buf, unsigned long long* refuted,
+    const uint32_t* __restrict__ list, const EcStreamParams p,
+    uint64_t stripe_bytes, uint64_t vecs_per_chunk, uint32_t tpc,
+    uint32_t step_e, uint32_t step_t, uint32_t cand) {
+  const uint32_t count = list[0];
+  if (count == 0u) return;
+  const uint32_t voff = threadIdx.x << 4;
+  const int n_src = p.n_src;
+  uint32_t one_mask[NOUT], mul_mask[NOUT];
+#pragma unroll
+  for (int j = 0; j < NOUT; j++) {
+    one_mask[j] = p.one_mask[j];
+    mul_mask[j] = p.mul_mask[j];
+  }
+  uint32_t e = blockIdx.x / tpc, tile = blockIdx.x % tpc;
+  while (e < count) {
+    const uint32_t stripe = list[1 + e];
+    const uint64_t tbase =
+        (uint64_t)stripe * stripe_bytes + ((uint64_t)tile << 12);
+    if (((uint64_t)tile << 8) + threadIdx.x < vecs_per_chunk) {
+      const uint8_t* sb = buf + tbase;
+      uint32_t acc[NOUT][4];
+#pragma unroll
+      for (int j = 0; j < NOUT; j++)
+        acc[j][0] = acc[j][1] = acc[j][2] = acc[j][3] = 0u;
+      ecx_stream_sources<NOUT>(p, one_mask, mul_mask, n_src, sb, voff, acc);
+      v4u st[NOUT];
+#pragma unroll
+      for (int j = 0; j < NOUT; j++)
+        st[j] = __builtin_nontemporal_load(
+            reinterpret_cast<const v4u*>(sb + p.out_off[j] + voff));
+      uint32_t diff = 0u;
+#pragma unroll
+      for (int j = 0; j < NOUT; j++)
+        diff |= (acc[j][0] ^ st[j].x) | (acc[j][1] ^ st[j].y) |
+                (acc[j][2] ^ st[j].z) | (acc[j][3] ^ st[j].w);
+      // wave-uniform, so the branch is scalar
+      const unsigned long long vote = __ballot(diff != 0u);
+      if (vote != 0ull &&
+          (threadIdx.x & 63u) == (uint32_t)__ffsll((long long)vote) - 1u)
+        atomicOr(&refuted[stripe], 1ull << cand);
+    }
+    // e + step_e stays far below 2^32: both are at most 65535 + 2^23
+    e += step_e;
+    tile += step_t;
+    if (tile >= tpc) {
+      tile -= tpc;
+      e++;
+    }
+  }
+}
+
+// d_culprit has collected the refuted bits; one lane per stripe turns it
+// into the culprit word (locate_word of locate_plan.h).
+template <int = 0>
+__global__ __launch_bounds__(256) void ec_locate_finish_kernel(
+    const unsigned long long* __restrict__ bad, unsigned long long* culprit,
+    uint64_t present_mask, uint64_t survivor_mask, uint32_t n_stripes) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n_stripes) return;
+  culprit[s] =
+      ecx::locate_word(present_mask, survivor_mask, bad[s], culprit[s]);
+}
+
+// ---------------------------------------------------------------------------
 // Host-side: context, streams, decode-row LRU, launches
 // ---------------------------------------------------------------------------
 
@@ -1379,6 +1493,10 @@ struct Slot {
   // host-path staging stripe buffer, grown on demand
   uint8_t* d_stage = nullptr;
   size_t stage_bytes = 0;
+  // ecx_locate_batch: the count of flagged stripes and their indices, grown
+  // on demand (at most 1 + 65535 words)
+  uint32_t* d_loc = nullptr;
+  size_t loc_words = 0;
   // pipelined host-path: pinned+device double buffer and resident
   // per-group launch params (see pipelined_matmul_host below)
   uint8_t* h_pipe = nullptr;  // pinned, 2 x cps x tile
@@ -1442,6 +1560,8 @@ struct ecx_ctx {
   // the same for ec_gf_verify_kernel, whose instances need not stay resident
   // in the same numbers
   std::atomic<int> verify_occ[5] = {};
+  // and for ec_gf_locate_kernel, whose grid is always the resident one
+  std::atomic<int> locate_occ[5] = {};
 
   bool is_bitmatrix() const {
     return technique == ECX_T_CAUCHY_ORIG_JERASURE ||
@@ -1560,6 +1680,7 @@ void ecx_destroy(ecx_ctx* ctx) {
     if (s.h_params) (void)hipHostFree(s.h_params);
     if (s.d_params) (void)hipFree(s.d_params);
     if (s.d_stage) (void)hipFree(s.d_stage);
+    if (s.d_loc) (void)hipFree(s.d_loc);
     if (s.h_pipe) (void)hipHostFree(s.h_pipe);
     if (s.d_pipe) (void)hipFree(s.d_pipe);
     if (s.h_pparams) (void)hipHostFree(s.h_pparams);
@@ -4135,6 +4256,302 @@ int ecx_crc32c_plan_probe(size_t chunk_bytes, long n_stripes, int n_chunks,
                      p.launches,  0};
   std::copy(v, v + 8, out);
   return ECX_OK;
+}
+
+}  // extern "C"
+
+// ---- locating the corrupt chunk: host side ----
+// At the end of the file for the reason given above run_crc.
+
+template <int NO>
+static hipError_t locate_occupancy(int* n) {
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      n, ec_gf_locate_kernel<NO>, 256, 0);
+}
+
+// One launch of ec_gf_locate_kernel: a pass of <= 4 checked chunks of one
+// candidate.
+struct LocateLaunch {
+  StreamLaunch L;  // argument block and sizes; its grid and walk are unused
+  uint32_t grid, tpc, step_e, step_t, cand;
+  int n_out;
+};
+
+// Locate plan of a mask (locate_plan.h), its decode plans through the LRU.
+static int get_locate_plan(ecx_ctx* ctx, uint64_t present_mask,
+                           ecx::LocatePlan& lp) {
+  auto resolve = [&](uint64_t mask, std::vector<int>& sv, std::vector<int>& er,
+                     std::vector<uint8_t>& rw) {
+    DecodePlan dp;
+    if (get_decode_plan(ctx, mask, dp) != ECX_OK) return false;
+    sv = std::move(dp.survivors);
+    er = std::move(dp.erased);
+    rw = std::move(dp.rows);
+    return true;
+  };
+  return verify_err(
+      ecx::plan_locate(ctx->k, ctx->m, present_mask, resolve, lp));
+}
+
+// Argument block and grid of one candidate pass. The host does not know how
+// many stripes are flagged, so the grid is what stays resident (CUs x blocks
+// per CU of this instance), capped by the tiles of the whole batch.
+static int locate_prepare(ecx_ctx* ctx, const ecx::VerifyPlan& cp, int j0,
+                          uint32_t cand, long n_stripes, size_t chunk_bytes,
+                          LocateLaunch& q) {
+  const int k = ctx->k, n = (int)cp.checked.size();
+  q.n_out = std::min(ECX_STREAM_MAX_OUT, n - j0);
+  q.cand = cand;
+  int r = stream_prepare(ctx, true, cp.survivors.data(), k,
+                         cp.checked.data() + j0, q.n_out,
+                         cp.rows.data() + (size_t)j0 * k, nullptr, n_stripes,
+                         chunk_bytes, q.L);
+  if (r != ECX_OK) return r;
+  int bpc = ctx->locate_occ[q.n_out].load();
+  if (bpc <= 0) {
+    hipError_t e = q.n_out == 1   ? locate_occupancy<1>(&bpc)
+                   : q.n_out == 2 ? locate_occupancy<2>(&bpc)
+                   : q.n_out == 3 ? locate_occupancy<3>(&bpc)
+                                  : locate_occupancy<4>(&bpc);
+    HIP_TRY(e);
+    bpc = std::max(1, bpc);
+    ctx->locate_occ[q.n_out].store(bpc);
+  }
+  const uint64_t tpc = (q.L.vecs + 255) / 256;  // < 2^31 (verify_check_args)
+  const uint64_t g = std::min<uint64_t>(
+      {tpc * (uint64_t)n_stripes,
+       (uint64_t)ctx->stream_cus.load() * (uint64_t)bpc, 1ull << 23});
+  q.grid = (uint32_t)std::max<uint64_t>(1, g);
+  q.tpc = (uint32_t)tpc;
+  q.step_e = q.grid / q.tpc;
+  q.step_t = q.grid % q.tpc;
+  return ECX_OK;
+}
+
+static int ensure_loc(ecx_ctx* ctx, Slot& s, size_t words) {
+  if (s.loc_words >= words) return ECX_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (s.d_loc) {
+    // earlier calls on this slot may still read the old list
+    HIP_TRY(hipStreamSynchronize(s.stream));
+    HIP_TRY(hipFree(s.d_loc));
+  }
+  s.d_loc = nullptr;
+  s.loc_words = 0;
+  HIP_TRY(hipMalloc(&s.d_loc, words * 4));
+  s.loc_words = words;
+  return ECX_OK;
+}
+
+// Both word arrays cleared, the verify passes into d_bad, the list of flagged
+// stripes, every candidate over that list, the finish rule; all on the slot's
+// stream with no host synchronisation. Arguments are validated and the slot
+// is locked by the caller; every pass is prepared before anything is
+// enqueued.
+static int run_locate(ecx_ctx* ctx, Slot& s, const uint8_t* d_buf,
+                      long n_stripes, size_t chunk_bytes,
+                      uint64_t present_mask, const ecx::LocatePlan& lp,
+                      uint64_t* d_bad, uint64_t* d_culprit) {
+  const int k = ctx->k;
+  std::vector<LocateLaunch> passes;
+  for (int i = 0; i < k; i++) {
+    const ecx::VerifyPlan& cp = lp.cand[i];
+    for (int j0 = 0; j0 < (int)cp.checked.size(); j0 += ECX_STREAM_MAX_OUT) {
+      passes.emplace_back();
+      int r = locate_prepare(ctx, cp, j0, (uint32_t)lp.base.survivors[i],
+                             n_stripes, chunk_bytes, passes.back());
+      if (r != ECX_OK) return r;
+    }
+  }
+  uint64_t survivor_mask = 0;
+  for (int sv : lp.base.survivors) survivor_mask |= 1ull << sv;
+  int r = ensure_loc(ctx, s, (size_t)n_stripes + 1);
+  if (r != ECX_OK) return r;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemsetAsync(d_culprit, 0, (size_t)n_stripes * 8, s.stream));
+  // clears d_bad and records the start event ahead of its first launch
+  r = run_verify(ctx, s, d_buf, n_stripes, chunk_bytes, lp.base, d_bad);
+  if (r != ECX_OK) return r;
+  auto* bad = (unsigned long long*)d_bad;
+  auto* cul = (unsigned long long*)d_culprit;
+  hipLaunchKernelGGL(ec_locate_list_kernel<>, dim3(1),
+                     dim3(ECX_LOCATE_LIST_T), 0, s.stream, bad, s.d_loc,
+                     (uint32_t)n_stripes);
+  HIP_TRY(hipGetLastError());
+  for (const LocateLaunch& q : passes) {
+    dispatch_nout(q.n_out, [&](auto NO) {
+      hipLaunchKernelGGL((ec_gf_locate_kernel<NO()>), dim3(q.grid), dim3(256),
+                         0, s.stream, d_buf, cul, s.d_loc, q.L.p,
+                         q.L.stripe_bytes, q.L.vecs, q.tpc, q.step_e, q.step_t,
+                         q.cand);
+    });
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(ec_locate_finish_kernel<>,
+                     dim3(((uint32_t)n_stripes + 255) / 256), dim3(256), 0,
+                     s.stream, bad, cul, present_mask, survivor_mask,
+                     (uint32_t)n_stripes);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(timer_stop(s));  // moves the stop event behind the last launch
+  return ECX_OK;
+}
+
+// Refusals of ecx_locate_batch that concern the two word arrays.
+static int locate_check_arrays(const ecx_ctx* ctx, const void* dptr,
+                               long n_stripes, size_t chunk_bytes,
+                               const uint64_t* d_bad,
+                               const uint64_t* d_culprit) {
+  if (!d_bad || !d_culprit) return ECX_ERR_INVAL;
+  if (((uintptr_t)d_bad | (uintptr_t)d_culprit) & 7) return ECX_ERR_INVAL;
+  const uintptr_t b0 = (uintptr_t)dptr;
+  const uintptr_t b1 =
+      b0 + (uintptr_t)n_stripes * (ctx->k + ctx->m) * chunk_bytes;
+  const uintptr_t w0 = (uintptr_t)d_bad, c0 = (uintptr_t)d_culprit;
+  const uintptr_t wn = (uintptr_t)n_stripes * 8;
+  if (w0 < b1 && b0 < w0 + wn) return ECX_ERR_INVAL;
+  if (c0 < b1 && b0 < c0 + wn) return ECX_ERR_INVAL;
+  if (w0 < c0 + wn && c0 < w0 + wn) return ECX_ERR_INVAL;
+  return ECX_OK;
+}
+
+extern "C" {
+
+int ecx_locate_batch(ecx_ctx* ctx, const void* dptr, long n_stripes,
+                     size_t chunk_bytes, uint64_t present_mask,
+                     uint64_t* d_bad, uint64_t* d_culprit, int slot) {
+  if (!ctx || !dptr || slot < 0 || slot >= (int)ctx->slots.size())
+    return ECX_ERR_INVAL;
+  int r = verify_check_args(ctx, n_stripes, chunk_bytes);
+  if (r != ECX_OK) return r;
+  r = locate_check_arrays(ctx, dptr, n_stripes, chunk_bytes, d_bad, d_culprit);
+  if (r != ECX_OK) return r;
+  ecx::LocatePlan lp;
+  r = get_locate_plan(ctx, present_mask, lp);
+  if (r != ECX_OK) return r;
+  Slot& s = ctx->slots[slot];
+  std::lock_guard<std::recursive_mutex> g(s.mu);
+  return run_locate(ctx, s, (const uint8_t*)dptr, n_stripes, chunk_bytes,
+                    present_mask, lp, d_bad, d_culprit);
+}
+
+int ecx_locate_chunks_host(ecx_ctx* ctx, const uint8_t* const* chunks,
+                           uint64_t present_mask, size_t chunk_bytes,
+                           uint64_t* bad, uint64_t* culprit) {
+  if (!ctx || !chunks || !bad || !culprit) return ECX_ERR_INVAL;
+  int r = verify_check_args(ctx, 1, chunk_bytes);
+  if (r != ECX_OK) return r;
+  ecx::LocatePlan lp;
+  r = get_locate_plan(ctx, present_mask, lp);
+  if (r != ECX_OK) return r;
+  const int cps = ctx->k + ctx->m;
+  for (int i = 0; i < cps; i++)
+    if ((present_mask >> i & 1) && !chunks[i]) return ECX_ERR_INVAL;
+  const int si = (int)(ctx->rr++ % ctx->slots.size());
+  Slot& s = ctx->slots[si];
+  std::lock_guard<std::recursive_mutex> g(s.mu);
+  // one stripe in the staging buffer, its two words behind it
+  const size_t cb = chunk_bytes, word_off = (size_t)cps * cb;
+  r = ensure_stage(ctx, s, word_off + 16);
+  if (r != ECX_OK) return r;
+  HIP_TRY(hipSetDevice(ctx->device));
+  for (int i = 0; i < cps; i++)
+    if (present_mask >> i & 1)
+      HIP_TRY(hipMemcpyAsync(s.d_stage + (size_t)i * cb, chunks[i], cb,
+                             hipMemcpyHostToDevice, s.stream));
+  uint64_t* d_words = (uint64_t*)(s.d_stage + word_off);
+  r = run_locate(ctx, s, s.d_stage, 1, cb, present_mask, lp, d_words,
+                 d_words + 1);
+  if (r != ECX_OK) {
+    (void)hipStreamSynchronize(s.stream);  // quiesce before buffer reuse
+    return r;
+  }
+  uint64_t words[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(words, d_words, 16, hipMemcpyDeviceToHost, s.stream));
+  HIP_TRY(wait_stream(s.stream));
+  *bad = words[0];
+  *culprit = words[1];
+  return ECX_OK;
+}
+
+int ecx_locate_plan_probe(int technique, int k, int m, uint64_t present_mask,
+                          int* survivors, int* checked, int* cand_survivors,
+                          int* cand_checked, uint8_t* cand_rows) {
+  // CPU-only: the planning ecx_locate_batch performs (same plan_locate, the
+  // decode plans composed directly instead of via a context's LRU). Outputs
+  // are written only on success.
+  if (!survivors || !checked || !cand_survivors || !cand_checked ||
+      !cand_rows || k < 1 || m < 1 || k + m > 64)
+    return ECX_ERR_INVAL;
+  if (technique != ECX_T_RS_VAN_ISA && technique != ECX_T_CAUCHY_ISA &&
+      technique != ECX_T_RS_VAN_JERASURE)
+    return ECX_ERR_INVAL;  // w=8 matrix techniques only, like the calls
+  std::vector<uint8_t> gen;
+  if (!ecx::gen_matrix(technique, gen, k, m)) return ECX_ERR_INVAL;
+  auto resolve = [&](uint64_t mask, std::vector<int>& sv, std::vector<int>& er,
+                     std::vector<uint8_t>& rw) {
+    return ecx::compose_decode_rows(gen, k, m, mask, sv, er, rw);
+  };
+  ecx::LocatePlan lp;
+  const int r = verify_err(ecx::plan_locate(k, m, present_mask, resolve, lp));
+  if (r != ECX_OK) return r;
+  const size_t n = lp.base.checked.size();
+  std::copy(lp.base.survivors.begin(), lp.base.survivors.end(), survivors);
+  std::copy(lp.base.checked.begin(), lp.base.checked.end(), checked);
+  for (int i = 0; i < k; i++) {
+    const ecx::VerifyPlan& cp = lp.cand[i];
+    std::copy(cp.survivors.begin(), cp.survivors.end(),
+              cand_survivors + (size_t)i * k);
+    std::copy(cp.checked.begin(), cp.checked.end(),
+              cand_checked + (size_t)i * (n - 1));
+    std::copy(cp.rows.begin(), cp.rows.end(),
+              cand_rows + (size_t)i * (n - 1) * k);
+  }
+  return (int)n;
+}
+
+uint64_t ecx_locate_word_probe(uint64_t present_mask, uint64_t survivor_mask,
+                               uint64_t bad, uint64_t refuted) {
+  return ecx::locate_word(present_mask, survivor_mask, bad, refuted);
+}
+
+int ecx_repair_batch(ecx_ctx* ctx, void* dptr, long n_stripes,
+                     size_t chunk_bytes, uint64_t present_mask,
+                     uint64_t* d_bad, uint64_t* d_culprit, long* n_repaired,
+                     long* n_unlocatable, int slot) {
+  if (!ctx || !n_repaired || !n_unlocatable || slot < 0 ||
+      slot >= (int)ctx->slots.size())
+    return ECX_ERR_INVAL;
+  // one lock over locate, the download and the decode, so that no other call
+  // on the slot comes between them
+  Slot& s = ctx->slots[slot];
+  std::lock_guard<std::recursive_mutex> g(s.mu);
+  int r = ecx_locate_batch(ctx, dptr, n_stripes, chunk_bytes, present_mask,
+                           d_bad, d_culprit, slot);
+  if (r != ECX_OK) return r;
+  std::vector<uint64_t> words((size_t)n_stripes * 2);
+  uint64_t* bad = words.data();
+  uint64_t* cul = bad + n_stripes;
+  HIP_TRY(hipMemcpyAsync(bad, d_bad, (size_t)n_stripes * 8,
+                         hipMemcpyDeviceToHost, s.stream));
+  HIP_TRY(hipMemcpyAsync(cul, d_culprit, (size_t)n_stripes * 8,
+                         hipMemcpyDeviceToHost, s.stream));
+  HIP_TRY(wait_stream(s.stream));  // the one synchronisation of the call
+  const int cps = ctx->k + ctx->m;
+  const uint64_t all = cps >= 64 ? ~0ull : ((1ull << cps) - 1);
+  long rep = 0, unl = 0;
+  // per stripe: the mask without its culprit, or every chunk present (nothing
+  // to rebuild, never written); the downloaded culprit words are reused
+  for (long i = 0; i < n_stripes; i++) {
+    const uint64_t c = cul[i];
+    const bool located = bad[i] != 0 && c != 0 && (c & (c - 1)) == 0;
+    rep += located;
+    unl += bad[i] != 0 && !located;
+    cul[i] = located ? present_mask & ~c : all;
+  }
+  *n_repaired = rep;
+  *n_unlocatable = unl;
+  if (rep == 0) return ECX_OK;  // nothing located, nothing launched
+  return ecx_decode_batch_multi(ctx, dptr, n_stripes, chunk_bytes, cul, slot);
 }
 
 }  // extern "C"

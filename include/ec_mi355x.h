@@ -23,6 +23,9 @@
  *   scrub's re-encode-and-compare (encode_chunks     src/erasure-code/ErasureCodeInterface.h
  *     into a second buffer, then a compare pass)       encode_chunks, as used by the OSD
  *     -> ecx_verify_batch()                            scrub path
+ *   naming and rebuilding the wrong shard of an      (no counterpart where the pool
+ *     inconsistent stripe                              keeps no HashInfo)
+ *     -> ecx_locate_batch(), ecx_repair_batch()
  *   ceph_crc32c over each shard                      src/osd/ECUtil.cc
  *     (ECUtil::HashInfo::append, EC deep scrub)        HashInfo::append
  *     -> ecx_crc32c_batch()
@@ -313,6 +316,90 @@ ECX_API int ecx_verify_plan_probe(int technique, int k, int m,
                                   uint64_t present_mask, int *survivors,
                                   int *checked, uint8_t *rows);
 
+/* ---------------- locate and repair (scrub) --------------------------------
+ * ecx_verify_batch says that a stripe is inconsistent, not which chunk is
+ * wrong: a damaged checked chunk sets its own bit, a damaged survivor sets
+ * every bit. Pools that keep per-shard hashes (HashInfo, ecx_crc32c_batch)
+ * answer "which shard" from those; pools with EC overwrites keep none. With
+ * two or more redundant chunks the code itself answers it. The whole
+ * contract, for survivors and checked chunks as ecx_verify_batch defines
+ * them:
+ *   bit x of d_culprit[s] is set exactly when x is present and
+ *   ecx_verify_batch under present_mask & ~(1 << x) would report 0 for
+ *   stripe s
+ * (leaving chunk x out makes the remaining chunks agree with each other),
+ * and d_bad[s] is exactly the word ecx_verify_batch writes under
+ * present_mask. For the MDS techniques this means: a clean stripe has
+ * d_bad 0 and d_culprit == present_mask; exactly one damaged chunk x,
+ * damaged anywhere and in any number of bytes, gives d_culprit == 1 << x;
+ * two chunks damaged in different byte columns give d_culprit == 0; and with
+ * d_bad != 0 the culprit word never has more than one bit. After
+ * ecx_set_matrix the code need not be MDS: the definition still holds, more
+ * than one bit is then possible, and callers treat that as "not located".
+ * What the algebra cannot see: with exactly two checked chunks, two chunks
+ * damaged in the same byte columns imitate a single damaged third chunk if,
+ * in every damaged column, the second error is the one value of 255 that
+ * fits the first; with three or more checked chunks two damaged chunks never
+ * look like one.
+ *
+ * Both arrays are device arrays of n_stripes 64-bit words, 8-byte aligned,
+ * outside the batch and disjoint from each other; the batch is never
+ * written. Work, all on the slot's stream with no host synchronisation:
+ * both arrays cleared, the passes of ecx_verify_batch, one launch that lists
+ * the flagged stripes, then for each of the k survivors ceil((checked-1)/4)
+ * launches that check "this survivor is the culprit" on the flagged stripes
+ * only (a clean batch: every block leaves after one load), one launch that
+ * forms the words. Leaving out a checked chunk needs no launch: its answer
+ * is d_bad without that bit. ecx_last_kernel_ms covers first launch to last.
+ * All validation precedes any GPU work and a refused call writes neither
+ * array: every refusal of ecx_verify_batch, applied to each array, and
+ * ECX_ERR_INVAL for arrays that overlap or are equal and for fewer than two
+ * checked chunks (every present chunk would qualify); ECX_ERR_IO for fewer
+ * than k present chunks and for a present_mask, or a present_mask less one
+ * survivor, whose first k chunks do not invert (possible after
+ * ecx_set_matrix). */
+ECX_API int ecx_locate_batch(ecx_ctx *ctx, const void *dptr, long n_stripes,
+                             size_t chunk_bytes, uint64_t present_mask,
+                             uint64_t *d_bad, uint64_t *d_culprit, int slot);
+/* CPU-only (no GPU context): the planning of the call above. survivors[k]
+ * and checked[] (room for m) as ecx_verify_plan_probe. Candidate i leaves
+ * out survivors[i]: cand_survivors[i*k ..] = its k survivors (the others
+ * plus checked[0], ascending), cand_checked[i*(n-1) ..] = the n-1 chunks it
+ * checks, cand_rows[(i*(n-1)+j)*k ..] = the row of its j-th checked chunk
+ * over its survivors, n = n_checked. Returns n_checked or -errno as the call
+ * (outputs are then left unwritten); w=8 matrix techniques only, the others
+ * return ECX_ERR_INVAL. */
+ECX_API int ecx_locate_plan_probe(int technique, int k, int m,
+                                  uint64_t present_mask, int *survivors,
+                                  int *checked, int *cand_survivors,
+                                  int *cand_checked, uint8_t *cand_rows);
+/* CPU-only: the rule the last launch applies per stripe. refuted has bit s
+ * set when the candidate without survivor s found a difference. Returns
+ * present_mask if bad == 0; otherwise (survivor_mask & ~refuted) together
+ * with every checked bit j for which (bad & ~(1 << j)) == 0. */
+ECX_API uint64_t ecx_locate_word_probe(uint64_t present_mask,
+                                       uint64_t survivor_mask, uint64_t bad,
+                                       uint64_t refuted);
+/* Check, locate and repair in one call. Runs ecx_locate_batch into the two
+ * arrays, then WAITS for the slot and downloads both (the one host
+ * synchronisation of the batch API besides ecx_sync; 16 bytes per stripe),
+ * and hands ecx_decode_batch_multi one mask per stripe on the same slot:
+ * present_mask & ~d_culprit[s] where d_bad[s] != 0 and the culprit word has
+ * exactly one bit, all k+m chunks otherwise. It returns with that decode
+ * enqueued, as ecx_decode_batch_multi does. A located stripe gets its
+ * culprit rebuilt, and its absent chunks too, as ecx_decode_batch would
+ * under that mask; clean and unlocatable stripes are never written. Nothing
+ * located: nothing more is launched. *n_repaired = the located stripes,
+ * *n_unlocatable = the stripes with d_bad != 0 that were not. The arrays
+ * keep the words of ecx_locate_batch, i.e. the state before the repair.
+ * Refusals as ecx_locate_batch, and ECX_ERR_INVAL for a NULL count pointer;
+ * after ecx_set_matrix a located stripe whose mask does not decode makes the
+ * call return ECX_ERR_IO with the arrays written and the batch untouched. */
+ECX_API int ecx_repair_batch(ecx_ctx *ctx, void *dptr, long n_stripes,
+                             size_t chunk_bytes, uint64_t present_mask,
+                             uint64_t *d_bad, uint64_t *d_culprit,
+                             long *n_repaired, long *n_unlocatable, int slot);
+
 /* ---------------- per-shard CRC-32C ----------------------------------------
  * The hash the OSD keeps per shard: ECUtil::HashInfo::append runs
  * ceph_crc32c(old_hash, shard_bytes, len) over each of the k+m shards of a
@@ -489,6 +576,14 @@ ECX_API int ecx_decode_chunks_host(ecx_ctx *ctx, uint8_t *const *chunks,
 ECX_API int ecx_verify_chunks_host(ecx_ctx *ctx, const uint8_t *const *chunks,
                                    uint64_t present_mask, size_t chunk_bytes,
                                    uint64_t *bad);
+
+/* ecx_locate_batch for one stripe in host memory, built like the call above:
+ * *bad and *culprit receive the stripe's two words. A NULL entry for a
+ * present id is ECX_ERR_INVAL. Uploads the present chunks, downloads 16
+ * bytes; same refusals as the batch call. */
+ECX_API int ecx_locate_chunks_host(ecx_ctx *ctx, const uint8_t *const *chunks,
+                                   uint64_t present_mask, size_t chunk_bytes,
+                                   uint64_t *bad, uint64_t *culprit);
 
 ECX_API int ecx_encode_delta_host(ecx_ctx *ctx, const uint8_t *old_data,
                                   const uint8_t *new_data, uint8_t *delta,
