@@ -14,8 +14,8 @@ oracle:
 
 core: ceph_amd/libec_mi355x_core.so
 
-ceph_amd/libec_mi355x_core.so: ceph_amd/csrc/ec_core.hip ceph_amd/csrc/gf.cpp ceph_amd/csrc/gf.h ceph_amd/csrc/decode_multi.cpp ceph_amd/csrc/decode_multi.h ceph_amd/csrc/update_plan.cpp ceph_amd/csrc/update_plan.h ceph_amd/csrc/verify_plan.cpp ceph_amd/csrc/verify_plan.h ceph_amd/csrc/locate_plan.cpp ceph_amd/csrc/locate_plan.h ceph_amd/csrc/crc_plan.cpp ceph_amd/csrc/crc_plan.h ceph_amd/csrc/bit_plan.cpp ceph_amd/csrc/bit_plan.h ceph_amd/csrc/stream_walk.h include/ec_mi355x.h
-	$(HIPCC) $(HIPFLAGS) -shared ceph_amd/csrc/ec_core.hip ceph_amd/csrc/gf.cpp ceph_amd/csrc/decode_multi.cpp ceph_amd/csrc/update_plan.cpp ceph_amd/csrc/verify_plan.cpp ceph_amd/csrc/locate_plan.cpp ceph_amd/csrc/crc_plan.cpp ceph_amd/csrc/bit_plan.cpp -o $@
+ceph_amd/libec_mi355x_core.so: ceph_amd/csrc/ec_core.hip ceph_amd/csrc/gf.cpp ceph_amd/csrc/gf.h ceph_amd/csrc/decode_multi.cpp ceph_amd/csrc/decode_multi.h ceph_amd/csrc/update_plan.cpp ceph_amd/csrc/update_plan.h ceph_amd/csrc/verify_plan.cpp ceph_amd/csrc/verify_plan.h ceph_amd/csrc/locate_plan.cpp ceph_amd/csrc/locate_plan.h ceph_amd/csrc/crc_plan.cpp ceph_amd/csrc/crc_plan.h ceph_amd/csrc/slice_plan.cpp ceph_amd/csrc/slice_plan.h ceph_amd/csrc/bit_plan.cpp ceph_amd/csrc/bit_plan.h ceph_amd/csrc/stream_walk.h include/ec_mi355x.h
+	$(HIPCC) $(HIPFLAGS) -shared ceph_amd/csrc/ec_core.hip ceph_amd/csrc/gf.cpp ceph_amd/csrc/decode_multi.cpp ceph_amd/csrc/update_plan.cpp ceph_amd/csrc/verify_plan.cpp ceph_amd/csrc/locate_plan.cpp ceph_amd/csrc/crc_plan.cpp ceph_amd/csrc/slice_plan.cpp ceph_amd/csrc/bit_plan.cpp -o $@
 
 # ---- plugin harness (standalone mirror of the reference's registry layer;
 #      plugins resolve base-class/registry symbols from the host binary at

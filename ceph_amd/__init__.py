@@ -101,6 +101,12 @@ def _lib():
         ctypes.c_int, ctypes.c_int, ctypes.c_int,
         ctypes.POINTER(ctypes.c_uint64), ctypes.c_long,
         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    lib.ecx_slice_plan_probe.argtypes = [
+        ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+        ctypes.POINTER(ctypes.c_size_t), ctypes.c_int,
+        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int),
+        ctypes.POINTER(ctypes.c_int), ctypes.c_long, ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_long), ctypes.c_void_p, ctypes.c_size_t]
     lib.ecx_update_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_long, ctypes.c_size_t,
                                      ctypes.c_void_p,
@@ -291,6 +297,61 @@ def decode_multi_plan_probe(technique, k, m, masks):
         pos.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
         ctypes.byref(n_plans)), "ecx_decode_multi_plan_probe")
     return r, pos[:len(a)], n_plans.value
+
+
+def slice_plan_probe(cps, chunk_ptrs, sizes, written_masks=None, order=None,
+                     recs=None, head=0):
+    """CPU-only: what the slice calls do on the host before anything is
+    enqueued, for n slices of cps chunk addresses each (integers, None or 0 =
+    NULL; never followed) and their sizes. written_masks[s] bit c = the call
+    writes chunk c of slice s. Raises EINVAL for what the calls refuse.
+    Returns a dict: vecs_per_block, n_blocks, the offsets off_* and bytes of
+    the job table behind `head`, and the table's arrays ptrs, slice_vecs,
+    block_voff, block_slice, block_rec (None without recs) and the whole
+    `blob` as the kernels would read them."""
+    what = "ecx_slice_plan_probe"
+    n = len(sizes)
+    arr = (ctypes.c_void_p * max(len(chunk_ptrs), 1))()
+    for i, p in enumerate(chunk_ptrs):
+        arr[i] = None if p in (None, 0) else int(p)
+    sz = (ctypes.c_size_t * max(n, 1))(*sizes)
+    wr = None
+    if written_masks is not None:
+        wa = _mask_array(written_masks, n, what)
+        wr = _u64p(wa)
+    i32p = ctypes.POINTER(ctypes.c_int)
+    oa = ra = None
+    if order is not None:
+        oa = np.ascontiguousarray(order, dtype=np.int32)
+    if recs is not None:
+        ra = np.ascontiguousarray(recs, dtype=np.int32)
+        if oa is None or len(ra) != len(oa):
+            raise EcError(f"{what}: recs needs an order of the same length")
+    op = None if oa is None else oa.ctypes.data_as(i32p)
+    rp = None if ra is None else ra.ctypes.data_as(i32p)
+    n_order = 0 if oa is None else len(oa)
+    out = (ctypes.c_long * 8)()
+    _ck(lib().ecx_slice_plan_probe(cps, arr, sz, n, wr, op, rp, n_order,
+                                   head, out, None, 0), what)
+    blob = np.zeros(out[7], dtype=np.uint8)
+    _ck(lib().ecx_slice_plan_probe(cps, arr, sz, n, wr, op, rp, n_order,
+                                   head, out, blob.ctypes.data_as(
+                                       ctypes.c_void_p), blob.nbytes), what)
+    g = dict(zip(("vecs_per_block", "n_blocks", "off_ptrs", "off_vecs",
+                  "off_voff", "off_bslice", "off_brec", "bytes"), out))
+    nb = g["n_blocks"]
+
+    def view(off, count, dt):
+        return blob[off:off + count * np.dtype(dt).itemsize].view(dt)
+
+    g.update(blob=blob,
+             ptrs=view(g["off_ptrs"], n * cps, np.uint64),
+             slice_vecs=view(g["off_vecs"], n, np.int64),
+             block_voff=view(g["off_voff"], nb, np.int64),
+             block_slice=view(g["off_bslice"], nb, np.int32),
+             block_rec=None if ra is None else view(g["off_brec"], nb,
+                                                    np.int32))
+    return g
 
 
 def update_plan_probe(k, m, masks):
@@ -527,13 +588,18 @@ class EcContext:
 
     def encode_slices(self, chunk_ptrs, sizes, slot=0):
         """Variable-size slice batch: chunk_ptrs is a flat list
-        of n*(k+m) device addresses (None => zeros data chunk); sizes is
-        the per-slice byte length (multiples of 16). One kernel launch."""
+        of n*(k+m) device addresses, multiples of 16 (None => zeros data
+        chunk; a parity address must not be None); sizes is the per-slice
+        byte length (multiples of 16). One kernel launch per <= 4 parity
+        chunks. A refused call (EINVAL) has launched nothing."""
         arr, sz, n = self._slice_args(chunk_ptrs, sizes)
         _ck(lib().ecx_encode_slices(self._h, arr, sz, n, slot),
             "ecx_encode_slices")
 
     def decode_slices(self, chunk_ptrs, sizes, present_mask, slot=0):
+        """encode_slices' counterpart under one present mask for the call:
+        the absent chunks of every slice are written (their addresses must
+        not be None); a present chunk may be None (zeros)."""
         arr, sz, n = self._slice_args(chunk_ptrs, sizes)
         _ck(lib().ecx_decode_slices(self._h, arr, sz, n, present_mask,
                                     slot), "ecx_decode_slices")

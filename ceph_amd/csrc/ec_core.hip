@@ -53,6 +53,7 @@
 #include "verify_plan.h"
 #include "locate_plan.h"
 #include "crc_plan.h"
+#include "slice_plan.h"
 #include "bit_plan.h"
 #include "stream_walk.h"
 
@@ -2312,11 +2313,8 @@ static int send_jobs(Slot& s, size_t bytes) {
   return ECX_OK;
 }
 
-static const int SLICE_VPB = 256 * 4;  // vectors per block, slice kernels
-
-static long slice_blocks(size_t bytes) {
-  return (long)((bytes >> 4) + SLICE_VPB - 1) / SLICE_VPB;
-}
+using ecx::SLICE_VPB;
+using ecx::slice_blocks;
 
 // Device addresses of a slice job table, and its extent in s.h_jobs.
 struct SliceJobs {
@@ -2329,70 +2327,43 @@ struct SliceJobs {
   size_t bytes;
 };
 
-// Build the slice kernels' job table in s.h_jobs behind `head` bytes the
-// caller keeps for launch records: [ptrs u64][slice_vecs i64][block_voff
-// i64][block_slice i32][block_rec i32]. Blocks are assigned to the slices
-// order[0..n_order) in that order (order == NULL: every slice once);
+// Build the slice kernels' job table (slice_plan.h) in s.h_jobs behind `head`
+// bytes the caller keeps for launch records. Blocks are assigned to the
+// slices order[0..n_order) in that order (order == NULL: every slice once);
 // recs[i], when given, is the record index of the blocks of order[i]. The
-// caller uploads s.h_jobs[0, bytes).
+// caller has checked the arguments and uploads s.h_jobs[0, bytes).
 static int build_slice_jobs(ecx_ctx* ctx, Slot& s, size_t head,
                             void* const* d_chunks, const size_t* bytes,
                             int n_slices, const int* order, const int* recs,
                             size_t n_order, SliceJobs* out) {
   const int cps = ctx->k + ctx->m;
-  long n_blocks = 0;
-  for (size_t i = 0; i < n_order; i++)
-    n_blocks += slice_blocks(bytes[order ? order[i] : (int)i]);
-  if (n_blocks > (1 << 30)) return ECX_ERR_INVAL;
-  const size_t off_vecs = head + (size_t)n_slices * cps * 8;
-  const size_t off_voff = off_vecs + (size_t)n_slices * 8;
-  const size_t off_bsl = off_voff + (size_t)n_blocks * 8;
-  const size_t off_brec = off_bsl + (size_t)n_blocks * 4;
-  const size_t blob = off_brec + (recs ? (size_t)n_blocks * 4 : 0);
-  int r = open_jobs(ctx, s, blob);
+  ecx::SliceLayout L;
+  if (!ecx::plan_slice_layout(cps, bytes, n_slices, order, n_order,
+                              recs != nullptr, head, L))
+    return ECX_ERR_INVAL;
+  int r = open_jobs(ctx, s, L.bytes);
   if (r != ECX_OK) return r;
-
-  uint64_t* ptrs = (uint64_t*)(s.h_jobs + head);
-  long* svecs = (long*)(s.h_jobs + off_vecs);
-  long* bvoff = (long*)(s.h_jobs + off_voff);
-  int* bslice = (int*)(s.h_jobs + off_bsl);
-  int* brec = (int*)(s.h_jobs + off_brec);
-  for (int i = 0; i < n_slices; i++) {
-    for (int c = 0; c < cps; c++)
-      ptrs[(size_t)i * cps + c] = (uint64_t)d_chunks[(size_t)i * cps + c];
-    svecs[i] = (long)(bytes[i] >> 4);
-  }
-  long b = 0;
-  for (size_t i = 0; i < n_order; i++) {
-    const int sl = order ? order[i] : (int)i;
-    for (long v = 0; v < svecs[sl]; v += SLICE_VPB) {
-      bslice[b] = sl;
-      bvoff[b] = v;
-      if (recs) brec[b] = recs[i];
-      b++;
-    }
-  }
-  *out = {(const uint64_t*)(s.d_jobs + head),
-          (const long*)(s.d_jobs + off_vecs),
-          (const long*)(s.d_jobs + off_voff),
-          (const int*)(s.d_jobs + off_bsl),
-          (const int*)(s.d_jobs + off_brec),
-          n_blocks,
-          blob};
+  ecx::fill_slice_tables((uint8_t*)s.h_jobs, L, cps, d_chunks, bytes,
+                         n_slices, order, recs, n_order);
+  *out = {(const uint64_t*)(s.d_jobs + L.off_ptrs),
+          (const long*)(s.d_jobs + L.off_vecs),
+          (const long*)(s.d_jobs + L.off_voff),
+          (const int*)(s.d_jobs + L.off_bslice),
+          (const int*)(s.d_jobs + L.off_brec),
+          L.n_blocks,
+          L.bytes};
   return ECX_OK;
 }
 
-// Launch the variable-size slice kernel in groups of <= 4 outputs.
+// Launch the variable-size slice kernel in groups of <= 4 outputs. The
+// caller has validated the slot and the arrays (slice_call_ok, check_slices);
+// the one refusal left, too many blocks, precedes the first enqueue too.
 static int run_slices(ecx_ctx* ctx, int slot_i, void* const* d_chunks,
                       const size_t* bytes, int n_slices, const int* src_ids,
                       int n_src, const int* out_ids, int n_out,
                       const uint8_t* coeff) {
-  if (!ctx || slot_i < 0 || slot_i >= (int)ctx->slots.size() ||
-      n_slices < 1 || n_src < 1 || n_src > ECX_MAX_K || n_out < 1)
-    return ECX_ERR_INVAL;
+  if (n_src < 1 || n_src > ECX_MAX_K || n_out < 1) return ECX_ERR_INVAL;
   const int cps = ctx->k + ctx->m;
-  for (int i = 0; i < n_slices; i++)
-    if (bytes[i] == 0 || bytes[i] % 16) return ECX_ERR_INVAL;
   Slot& s = ctx->slots[slot_i];
   std::lock_guard<std::recursive_mutex> g(s.mu);
   HIP_TRY(hipSetDevice(ctx->device));
@@ -2870,11 +2841,24 @@ int ecx_apply_delta_dev(ecx_ctx* ctx, const void* d_delta, int data_shard,
                     src_ids, 1, out_ids, 1, coeff, nullptr, 1, bytes, true);
 }
 
+// What every slice call refuses before it looks at the arrays' contents.
+static bool slice_call_ok(ecx_ctx* ctx, void* const* d_chunks,
+                          const size_t* bytes, int slot) {
+  return ctx && d_chunks && bytes && slot >= 0 &&
+         slot < (int)ctx->slots.size() && !ctx->is_bitmatrix() &&
+         !ctx->is_w16();
+}
+
+static uint64_t low_mask(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1; }
+
 int ecx_encode_slices(ecx_ctx* ctx, void* const* d_chunks,
                       const size_t* bytes, int n_slices, int slot) {
-  if (!ctx || !d_chunks || !bytes || ctx->is_bitmatrix() || ctx->is_w16())
-    return ECX_ERR_INVAL;
+  if (!slice_call_ok(ctx, d_chunks, bytes, slot)) return ECX_ERR_INVAL;
   int k = ctx->k, m = ctx->m;
+  // parity chunks k..k+m-1 of every slice are written
+  const uint64_t written = low_mask(k + m) & ~low_mask(k);
+  if (!ecx::check_slices(k + m, d_chunks, bytes, n_slices, &written, 0))
+    return ECX_ERR_INVAL;
   int src_ids[ECX_MAX_K], out_ids[ECX_MAX_K];
   stripe_ids(k, m, src_ids, out_ids);
   return run_slices(ctx, slot, d_chunks, bytes, n_slices, src_ids, k,
@@ -2884,11 +2868,19 @@ int ecx_encode_slices(ecx_ctx* ctx, void* const* d_chunks,
 int ecx_decode_slices(ecx_ctx* ctx, void* const* d_chunks,
                       const size_t* bytes, int n_slices,
                       uint64_t present_mask, int slot) {
-  if (!ctx || !d_chunks || !bytes || ctx->is_bitmatrix() || ctx->is_w16())
+  if (!slice_call_ok(ctx, d_chunks, bytes, slot) ||
+      !ecx::check_slice_sizes(bytes, n_slices))
     return ECX_ERR_INVAL;
   DecodePlan plan;
   int r = get_decode_plan(ctx, present_mask, plan);
   if (r != ECX_OK) return r;
+  // the erased chunks of every slice are written; a full mask still has its
+  // pointers checked before it returns
+  uint64_t written = 0;
+  for (int e : plan.erased) written |= 1ull << e;
+  if (!ecx::check_slice_ptrs(ctx->k + ctx->m, d_chunks, n_slices, &written,
+                             0))
+    return ECX_ERR_INVAL;
   if (plan.erased.empty()) return ECX_OK;
   return run_slices(ctx, slot, d_chunks, bytes, n_slices,
                     plan.survivors.data(), ctx->k, plan.erased.data(),
@@ -2965,12 +2957,9 @@ int ecx_decode_batch_multi(ecx_ctx* ctx, void* dptr, long n_stripes,
 int ecx_decode_slices_multi(ecx_ctx* ctx, void* const* d_chunks,
                             const size_t* bytes, int n_slices,
                             const uint64_t* present_masks, int slot) {
-  if (!ctx || !d_chunks || !bytes || !present_masks || slot < 0 ||
-      slot >= (int)ctx->slots.size() || ctx->is_bitmatrix() ||
-      ctx->is_w16() || n_slices < 1)
+  if (!slice_call_ok(ctx, d_chunks, bytes, slot) || !present_masks ||
+      !ecx::check_slice_sizes(bytes, n_slices))
     return ECX_ERR_INVAL;
-  for (int i = 0; i < n_slices; i++)
-    if (bytes[i] == 0 || bytes[i] % 16) return ECX_ERR_INVAL;
   const int k = ctx->k, cps = ctx->k + ctx->m;
   Slot& s = ctx->slots[slot];
   std::lock_guard<std::recursive_mutex> g(s.mu);
@@ -2982,11 +2971,12 @@ int ecx_decode_slices_multi(ecx_ctx* ctx, void* const* d_chunks,
   if (r != ECX_OK) return r;
   // an erased chunk is written: it needs a buffer (NULL only ever means a
   // zeros SOURCE)
-  for (int i = 0; i < n_slices; i++) {
-    const int pl = grp.plan_of_stripe[i];
-    if (pl < 0) continue;
-    for (int e : plans[pl].erased)
-      if (!d_chunks[(size_t)i * cps + e]) return ECX_ERR_INVAL;
+  {
+    std::vector<uint64_t> written((size_t)n_slices);
+    for (int i = 0; i < n_slices; i++)
+      written[i] = ~present_masks[i] & low_mask(cps);
+    if (!ecx::check_slice_ptrs(cps, d_chunks, n_slices, written.data(), 1))
+      return ECX_ERR_INVAL;
   }
   if (grp.launches.empty()) return ECX_OK;
 
@@ -3055,6 +3045,37 @@ int ecx_decode_multi_plan_probe(int technique, int k, int m,
   std::memcpy(plan_of_stripe, grp.plan_of_stripe.data(), (size_t)n * 4);
   *n_plans = (int)grp.masks.size();
   return (int)grp.launches.size();
+}
+
+int ecx_slice_plan_probe(int cps, void* const* chunks, const size_t* bytes,
+                         int n_slices, const uint64_t* written_masks,
+                         const int* order, const int* recs, long n_order,
+                         size_t head, long out[8], void* blob,
+                         size_t blob_cap) {
+  // CPU-only: the check, the layout and the table fill of the slice calls
+  // (slice_plan.h), into a host buffer of exactly the blob's size. Outputs
+  // are written only on success.
+  if (!out || cps < 1 || cps > 64 || (recs && !order) ||
+      (order && n_order < 0) || (blob_cap && !blob))
+    return ECX_ERR_INVAL;
+  if (!ecx::check_slices(cps, chunks, bytes, n_slices, written_masks, 1))
+    return ECX_ERR_INVAL;
+  ecx::SliceLayout L;
+  if (!ecx::plan_slice_layout(cps, bytes, n_slices, order, (size_t)n_order,
+                              recs != nullptr, head, L))
+    return ECX_ERR_INVAL;
+  if (blob_cap) {
+    std::vector<uint8_t> tab(L.bytes, 0);
+    ecx::fill_slice_tables(tab.data(), L, cps, chunks, bytes, n_slices, order,
+                           recs, (size_t)n_order);
+    std::memcpy(blob, tab.data(), std::min(blob_cap, L.bytes));
+  }
+  const long o[8] = {SLICE_VPB,          L.n_blocks,
+                     (long)L.off_ptrs,   (long)L.off_vecs,
+                     (long)L.off_voff,   (long)L.off_bslice,
+                     (long)L.off_brec,   (long)L.bytes};
+  std::memcpy(out, o, sizeof(o));
+  return ECX_OK;
 }
 
 int ecx_update_batch(ecx_ctx* ctx, void* dptr, long n_stripes,

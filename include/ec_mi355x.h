@@ -199,13 +199,27 @@ ECX_API int ecx_apply_delta_dev(ecx_ctx *ctx, const void *d_delta,
  * Arrays are host-side, length n_slices:
  *   d_chunks[s*(k+m)+c] = device pointer to chunk c of slice s (data
  *     0..k-1 may be NULL => zeros);
- *   bytes[s] = slice length (multiple of 16).
+ *   bytes[s] = slice length (nonzero multiple of 16).
  * Encode: parity pointers k..k+m-1 are written.
+ * The kernels load and store 16 B vectors through the pointers as given, so
+ * every non-NULL chunk pointer must be a multiple of 16. NULL is legal only
+ * for a chunk the call reads (it then stands for a chunk of zeros, for that
+ * slice alone); a chunk the call writes needs a buffer: for encode the
+ * parity chunks k..k+m-1 of every slice. All validation precedes the first
+ * enqueue, and a refused call launches nothing: ECX_ERR_INVAL for a NULL
+ * array, a slot out of range, a bitmatrix or w=16 context, n_slices < 1, a
+ * size that is 0 or no multiple of 16, a misaligned pointer, or a NULL
+ * pointer for a written chunk.
  */
 ECX_API int ecx_encode_slices(ecx_ctx *ctx, void *const *d_chunks,
                               const size_t *bytes, int n_slices, int slot);
 
-/* Same for decode under a per-call uniform erasure pattern. */
+/* Same for decode under a per-call uniform erasure pattern: the chunks
+ * absent from present_mask are written in every slice and must not be NULL;
+ * a present chunk may be NULL (zeros). Refusals as above, checked in the
+ * order slot and arrays, sizes, mask (ECX_ERR_IO if undecodable), pointers —
+ * all before the first enqueue, and also when the mask erases nothing (such
+ * a valid call returns ECX_OK and launches nothing). */
 ECX_API int ecx_decode_slices(ecx_ctx *ctx, void *const *d_chunks,
                               const size_t *bytes, int n_slices,
                               uint64_t present_mask, int slot);
@@ -222,8 +236,11 @@ ECX_API int ecx_decode_slices(ecx_ctx *ctx, void *const *d_chunks,
  * by how many chunks they lose, not by which). All validation precedes the
  * first launch: ECX_ERR_IO if ANY mask is undecodable, ECX_ERR_INVAL for a
  * NULL pointer, bad slot, chunk_bytes % 16, n_stripes outside 1..65535, a
- * bitmatrix or w=16 context (as for ecx_*_slices) or, for slices, a NULL
- * pointer for an erased chunk — in each case nothing has been launched.
+ * bitmatrix or w=16 context (as for ecx_*_slices) or, for slices, a size
+ * that is 0 or no multiple of 16, a chunk pointer that is no multiple of 16
+ * or a NULL pointer for an erased chunk of that slice's mask (a present
+ * chunk may be NULL: zeros) — in each case nothing has been launched. For
+ * slices the order is slot and arrays, sizes, masks, pointers.
  * ecx_last_kernel_ms then covers the whole call (first launch to last). */
 ECX_API int ecx_decode_batch_multi(ecx_ctx *ctx, void *dptr, long n_stripes,
                                    size_t chunk_bytes,
@@ -240,6 +257,27 @@ ECX_API int ecx_decode_slices_multi(ecx_ctx *ctx, void *const *d_chunks,
 ECX_API int ecx_decode_multi_plan_probe(int technique, int k, int m,
                                         const uint64_t *present_masks, long n,
                                         int *plan_of_stripe, int *n_plans);
+/* CPU-only (no GPU context): the host side of the three slice calls before
+ * anything is enqueued — the argument check, the cut into blocks and the job
+ * table. cps = k + m; chunks[n_slices * cps] and bytes[n_slices] as for the
+ * calls (the pointers are only looked at, never followed); written_masks[s]
+ * bit c set => the call writes chunk c of slice s (NULL: nothing written).
+ * Blocks are assigned to the slices order[0..n_order) in that order (NULL:
+ * every slice once); recs[i], if given, is the launch record of the blocks
+ * of order[i]; head = bytes kept in front of the table for the records, a
+ * multiple of 8. out = {vectors per block, n_blocks, offsets of ptrs,
+ * slice_vecs, block_voff, block_slice, block_rec in the table, table bytes};
+ * the first min(blob_cap, table bytes) bytes of the table go to blob (head
+ * zeroed). ECX_ERR_INVAL for whatever the calls refuse on these arguments,
+ * an order entry outside 0..n_slices-1, recs without order, more than 2^30
+ * blocks or a head that is no multiple of 8 (outputs are then left
+ * unwritten). */
+ECX_API int ecx_slice_plan_probe(int cps, void *const *chunks,
+                                 const size_t *bytes, int n_slices,
+                                 const uint64_t *written_masks,
+                                 const int *order, const int *recs,
+                                 long n_order, size_t head, long out[8],
+                                 void *blob, size_t blob_cap);
 
 /* ---------------- per-stripe write sets (write batching) ------------------
  * The partial-write counterpart of the per-stripe erasure patterns above: a

@@ -138,6 +138,29 @@ def child():
         finally:
             ctx.close()
         assert np.array_equal(got, want), ("decode_batch_multi", tech, k, m)
+
+    # decode_slices and decode_slices_multi over scattered arenas
+    # (slices_cases.py), whole arena against the reference-encoded one:
+    # (4,6) with a second launch, a NULL survivor, sizes 16 / 4112 / 16400
+    import slices_cases as sc
+    ctx = ceph_amd.EcContext(4, 6, "cauchy", device=0)
+    try:
+        arena, truth, mask = sc.knob_decode_case()
+        dev = t.Dev(ctx, sc.erase(arena, truth, [mask] * arena.n))
+        ctx.decode_slices(arena.ptrs(dev.d.value), arena.sizes, mask)
+        ctx.sync()
+        got = dev.get(truth.shape)
+        dev.free()
+        assert np.array_equal(got, truth), "decode_slices, scattered"
+        arena, truth, masks = sc.knob_multi_case()
+        dev = t.Dev(ctx, sc.erase(arena, truth, masks))
+        ctx.decode_slices_multi(arena.ptrs(dev.d.value), arena.sizes, masks)
+        ctx.sync()
+        got = dev.get(truth.shape)
+        dev.free()
+        assert np.array_equal(got, truth), "decode_slices_multi, scattered"
+    finally:
+        ctx.close()
     print("KNOBS_OK")
 
 
